@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the Sonar hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, pre-warms, warms up, times the K steps and prints the headline line (`roofline` there comes from the timed
+region itself).  `--full` also measures everything else the line can carry, each in runs of its own after the timed region: the
+cold figure, `extra` and `roofline.kernels` (the other rows and BASELINE configurations), `cpu_baseline` and, at N > 1, the
+per-rank configurations and the final gather.  `--dump-outputs DIR` writes what the last timed step returned (rank 0's shard) as
+.npy files: a fixed, seeded sample of whole latents in float32 and every latent's mean and standard deviation in float64.  The
+inputs depend on the arguments alone (torch.manual_seed(0) fixes the generate-mode Philox streams), with or without `--full`.
 
 Metric (BASELINE.json): noise-latents/sec on SDXL 4x128x128 latents.  One "step" = one call of the normalised power-law (pink,
 alpha = 1) rFFT noise sampler for a batch of 512 latents per GPU (cfg2 of BASELINE.json at the north_star's batch), through the
@@ -19,7 +26,7 @@ Before the W warm-up steps the contract asks for, `--prewarm` (default 1000) unt
 the step time falls from ~67 us in the first milliseconds of a process to 60.5 us after ~30 ms of work and stays there
 (scratch/warm_curve.py); `config.prewarm_steps` records it.  `--prewarm 0` measures the cold figure.
 
-Prints ONE JSON line (rank 0).  Keys beyond the contract:
+Prints ONE JSON line (rank 0).  Keys beyond the contract (`kernels`, `cpu_baseline` and `extra` with `--full` only):
   roofline      the dominant launch pair (statistics pass + final pass of one C-ABI call), HIP-event timed on the launch stream
                 inside the timed region.  `achieved` / `frac` are at the bytes the kernels REALLY move (4N per latent: one write;
                 `traffic` = the rocprofv3 PMC figure from profiles/r02_traffic.json); `frac_contract_12N` is the same time priced
@@ -433,6 +440,25 @@ def secondary_rows(device, hl, pn, ng, nz, x, sig):
     return kernels, extra
 
 
+DUMP_LATENTS = 64  # latents of the step's output written whole by --dump-outputs: 64 x 4 x 128 x 128 float32 = 16 MB
+
+
+def dump_outputs(path, noise):
+    """--dump-outputs: what the caller of the timed path received from its last step.  The whole batch is 128 MB, so a fixed sample of
+    DUMP_LATENTS latents (numpy seed 0, the same indices every run) goes out whole, beside every latent's mean and standard deviation."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    b = noise.shape[0]
+    idx = np.sort(np.random.default_rng(0).choice(b, size=min(DUMP_LATENTS, b), replace=False))
+    sample = noise[torch.from_numpy(idx).to(noise.device)].float().cpu().numpy()
+    flat = noise.reshape(b, -1).double()
+    stats = torch.stack([flat.mean(1), flat.std(1)], 1).cpu().numpy()
+    np.save(os.path.join(path, "noise_sample.npy"), sample)                             # [64, 4, 128, 128] float32
+    np.save(os.path.join(path, "noise_sample_index.npy"), idx.astype(np.float64))      # which latents of the batch those are
+    np.save(os.path.join(path, "noise_latent_stats.npy"), stats)                        # [512, 2] float64: mean, std of every latent
+
+
 def cfg5_shard_step_ms(device, hl, pn, nz, sonar):
     """cfg5 on one rank's shard (128 Flux latents): scheduled power + Perlin + Brownian chain, SonarDPMPPSDE with momentum; ms per sampler step
     (5 steps per run: 10 noise calls, 10 stand-in model evaluations)."""
@@ -542,12 +568,20 @@ def main():
                          "(scratch/warm_curve.py: 67 us per step cold, 60.5 us from step ~400 on)")
     ap.add_argument("--no-lookahead", action="store_true",
                     help="every call launches its own statistics pass (the sampler is given no PowerLookahead)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the cold figure, the other rows and configurations (extra, roofline.kernels), "
+                         "the CPU baseline and, at N > 1, the per-rank configurations and the final gather")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave extra and roofline.kernels out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's shard) to DIR/*.npy: a fixed sample of whole latents "
+                         "(float32) and every latent's mean and standard deviation (float64)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus)  # does not return
 
@@ -607,11 +641,6 @@ def main():
             item.stats_lookahead = lookahead
             return item.make_noise_sampler(x, None, None, seed=None, cpu=False, normalized=True)
 
-        ns = make_sampler(not args.no_lookahead)
-
-        def step():
-            return ns(*sig)
-
         # HIP events on the launch stream (torch's current stream is the stream every sonar_* call launches on) bracket the
         # timed region: average launch-pair duration = event span / steps.  (Per-call event pairs perturb the pipeline:
         # they add ~10 us of idle time per step.)  The events are created and recorded once before the region: the first
@@ -619,16 +648,28 @@ def main():
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
         ev1.record()
-        # the cold figure (what `--prewarm 0` measures): W + K steps from an idle GPU, before the clock ramp below
-        for _ in range(args.warmup):
-            step()
-        torch.cuda.synchronize()
-        ev0.record()
-        for _ in range(args.steps):
-            step()
-        ev1.record()
-        torch.cuda.synchronize()
-        cold_us = ev0.elapsed_time(ev1) / args.steps * 1e3
+        cold_us = None
+        if args.full:
+            # the cold figure (what `--prewarm 0` measures): W + K steps from an idle GPU, before the clock ramp below, on a sampler of
+            # its own; re-seeding afterwards hands the timed sampler the same Philox streams as in a plain run
+            ns_cold = make_sampler(not args.no_lookahead)
+            for _ in range(args.warmup):
+                ns_cold(*sig)
+            torch.cuda.synchronize()
+            ev0.record()
+            for _ in range(args.steps):
+                ns_cold(*sig)
+            ev1.record()
+            torch.cuda.synchronize()
+            cold_us = ev0.elapsed_time(ev1) / args.steps * 1e3
+            del ns_cold
+            torch.manual_seed(0)
+
+        ns = make_sampler(not args.no_lookahead)
+
+        def step():
+            return ns(*sig)
+
         for _ in range(max(args.prewarm, 0)):  # clock ramp, outside the W + K steps of the contract
             step()
         torch.cuda.synchronize()
@@ -641,7 +682,7 @@ def main():
         t0 = time.perf_counter()
         ev0.record()
         for _ in range(args.steps):
-            step()
+            last = step()
         ev1.record()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
@@ -700,7 +741,9 @@ def main():
                 "path": {"step_GBps_real_4N": real_bytes / step_s / 1e9, "step_GBps_at_12N": contract_bytes / step_s / 1e9,
                          "host_us_per_step_beyond_gpu": max(0.0, step_s * 1e6 - pair_us)},
             }
-    if rank == 0 and n_gpus == 1 and not args.no_extra:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_extra:
         kernels, extra = secondary_rows(device, hl, pn, ng, nz, x, sig)
         ns_two = make_sampler(False)
         extra["power_noise_cold_us"] = cold_us
@@ -715,9 +758,9 @@ def main():
         extra["bursts"] = BURSTS
         out["roofline"]["kernels"] = kernels
         out["extra"] = extra
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline:
+    if rank == 0 and n_gpus == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
-    if distributed and not args.no_extra:
+    if distributed and args.full and not args.no_extra:
         # N > 1: the two configurations BASELINE.json defines beside the headline, on EVERY rank's own shard -- cfg5 is an 8-GPU job of 128
         # Flux latents per rank, cfg3's chain runs at its configured 64 -- with the slowest and fastest rank in the line
         sonar_mod = importlib.import_module("comfyui_sonar_amd.py.sonar")
@@ -766,7 +809,7 @@ def main():
                               "hsa_enable_ipc_mode_legacy": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")}
     if rank == 0 and ranks is not None:
         out["ranks"] = ranks
-    if distributed:
+    if distributed and args.full:
         # optional final gather, outside `value`: RCCL all-gather vs direct peer-to-peer copies over xGMI, reported
         # under extra.gather.  Every rank learns whether all ranks succeeded before the next collective.  The result line waits for
         # it, so a watchdog on rank 0 prints the line without the gather figures if a collective hangs (the process group's own
@@ -821,8 +864,12 @@ def main():
             emit(gather)
         dist.barrier()
         dist.destroy_process_group()
-    elif rank == 0:
-        print(json.dumps(out), flush=True)
+    else:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if distributed:
+            dist.barrier()
+            dist.destroy_process_group()
 
 
 if __name__ == "__main__":

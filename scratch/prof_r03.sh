@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 cd "$(dirname "$0")/.."
 O=gpurun_out/r03
 rm -rf $O; mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python bench.py --no-cpu-baseline > $O/trace.log 2>&1
+python bench.py --full > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python bench.py --full --no-cpu-baseline > $O/trace.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $c -d $O/pmc_$c -o p -- python scratch/prof_workload.py > $O/pmc_$c.log 2>&1
 done

@@ -4,7 +4,7 @@ programs started by torch.distributed.run).
     gather_batch (ring all-gather and direct peer copies) against the single-process result, single generators and cfg5's chain;
   * the same worker with two ranks SHARING cuda:0 over gloo (collectives staged through the host): every kernel and every line of
     host code of the sharded path runs on a one-GPU box;
-  * `bench.py --gpus 2` as the driver calls it: starts its own ranks, reports n_gpus from the process group, a `ranks` list and the
+  * `bench.py --gpus 2 --full`: starts its own ranks, reports n_gpus from the process group, a `ranks` list and the
     gather timings under `extra` (gloo / shared GPU here; over RCCL when two GPUs exist)."""
 import json
 import os
@@ -42,17 +42,17 @@ def test_two_ranks_sharing_one_gpu_match_one_process():
     _run_worker("gloo")
 
 
-def _bench(n, backend):
+def _bench(n, backend, *extra_args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", SONAR_BENCH_BACKEND=backend)
     env.pop("WORLD_SIZE", None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--prewarm", "0"],
-                         env=env, capture_output=True, text=True, timeout=900)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--prewarm", "0",
+                          *extra_args], env=env, capture_output=True, text=True, timeout=900)
     return res
 
 
 def test_bench_starts_its_own_ranks():
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
-    res = _bench(2, backend)
+    res = _bench(2, backend, "--full")  # the per-rank configurations and the gather are measured with --full
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout[-2000:]

@@ -239,8 +239,8 @@ def test_spectral_gain_generators(golden):
     g = golden("spectral")
     d1, d2 = g["draw1"], g["draw2"]
 
-    def near(a, b):
-        close(a, b, rtol=0, atol=4e-6 * float(b.abs().max()))
+    def near(a, b, peak=None):
+        close(a, b, rtol=0, atol=4e-6 * (float(b.abs().max()) if peak is None else peak))
 
     sn = lambda t: orc.scale_noise(t, 1.0, normalized=True)  # noqa: E731
     near(orc.onef_noise(d1, alpha=-0.5), g["onef_pinkish_0"])
@@ -252,7 +252,13 @@ def test_spectral_gain_generators(golden):
     near((sn(orc.green_test_noise(d1)).mul_(0.75) + sn(orc.green_test_noise(d2)).mul_(0.5)).mul_(1.15), g["rainbow_intense_0"])
     close(g["pink_old_0"], d1)
     for name, kw in ONEF_ADV.items():
-        near(orc.onef_noise(d1, **kw), g["adv_" + name])
+        # onef_noise returns the real part of a complex inverse transform; its rounding scales with that transform's peak.  A gain
+        # that is negative under the square root (k < 0) makes the transform almost purely imaginary (neg_k: peak 6.3), and the real
+        # part is the plane means (0.07) plus rounding of the imaginary part, which differs from one host's FFT to another's.  So:
+        # every value relative to the transform's peak (oracle(i x) = -Im), the plane means relative to the real part's peak.
+        got, want = orc.onef_noise(d1, **kw), g["adv_" + name]
+        near(got, want, peak=max(float(want.abs().max()), float(torch.hypot(got, orc.onef_noise(d1 * 1j, **kw)).max())))
+        close(got.mean((-2, -1)), want.mean((-2, -1)), rtol=0, atol=4e-6 * float(want.abs().max()))
     near(orc.spectral_filter(g["pf_draw"], g["pf_a_filter"]), g["pf_a_0"])
     near(sn(orc.spectral_filter(g["pf_draw"], g["pf_a_filter"])), g["pf_a_1"])
 

@@ -115,3 +115,29 @@ def test_bench_annotations_survive_a_damaged_profile_file(tmp_path, monkeypatch)
     assert bench.traffic_table() == {}
     (tmp_path / "profiles" / "r05_pmc_issue_a.txt").write_text("void sonar::power_pipe_kernel<128, 128, false, true>\n  SQ_ACTIVE_INST_VALU\n")
     assert bench.valu_active_per_launch() is None
+
+
+def test_bench_dump_outputs_writes_a_fixed_bounded_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 / float64 .npy files under 64 MB in all, the same latents sampled every time."""
+    import importlib.util
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("sonar_bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    noise = torch.randn(512, 4, 128, 128, generator=torch.Generator().manual_seed(5))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), noise)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["noise_latent_stats.npy", "noise_sample.npy", "noise_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 1024 * 1024
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    idx = np.load(tmp_path / "a" / "noise_sample_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "noise_sample.npy"), noise[torch.from_numpy(idx)].numpy())
+    stats = np.load(tmp_path / "a" / "noise_latent_stats.npy")
+    np.testing.assert_allclose(stats[:, 0], noise.double().reshape(512, -1).mean(1).numpy(), atol=1e-12)
+    np.testing.assert_allclose(stats[:, 1], noise.double().reshape(512, -1).std(1).numpy(), rtol=1e-12)
