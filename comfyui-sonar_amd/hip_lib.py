@@ -1710,7 +1710,7 @@ class _Recorder:
         self.seed = None
         self.base = None      # first RNG stream id the call took
         self.count = 0        # stream ids taken
-        self.hooks = []       # PlanHook objects registered by wrappers whose arguments follow host state (power look-ahead)
+        self.hooks = []       # PlanHook objects: the power look-ahead wrapper's, and the look-ahead forms the peepholes put in
         self.failed = None
 
     def fail(self, why: str):
@@ -1745,19 +1745,15 @@ def load_raw() -> C.CDLL:
 
 
 class PlanHook:
-    """A wrapper whose arguments follow host state between calls (the power-law look-ahead) takes part in a plan through this protocol:
-    ``managed`` maps the addresses it supplies per call to names, ``bind`` learns their slot numbers, ``pre_run`` decides whether the
-    recorded call is still the right one and fills its slots, ``post_run`` updates the host state as the ordinary path would."""
+    """A wrapper whose arguments follow host state between calls (the look-ahead forms) takes part in a plan through this protocol:
+    ``managed`` maps the addresses it supplies per call to names, ``bind`` learns their slot numbers, ``pre_run(seed, base, table,
+    stream)`` decides whether the recorded call is still the right one and fills its slots -- None declines the call, anything else is
+    this call's token -- and ``post_run(token)`` updates the host state as the ordinary path would.  Nothing of one call is kept on the
+    hook in between."""
 
     managed: dict = {}
 
     def bind(self, slot_of: dict):
-        raise NotImplementedError
-
-    def pre_run(self, seed: int, base: int, slots, stream: int) -> bool:
-        raise NotImplementedError
-
-    def post_run(self, seed: int, base: int):
         pass
 
 
@@ -1771,7 +1767,6 @@ class _PowerAheadHook(PlanHook):
         self.managed = {ws.data_ptr(): "ws", nws.data_ptr(): "nws"}
         self.pair = None
         self.flip = 0
-        self.now = None
 
     def bind(self, slot_of):
         self.ws_slot, self.nws_slot = slot_of["ws"], slot_of["nws"]
@@ -1781,7 +1776,7 @@ class _PowerAheadHook(PlanHook):
         stream = base + self.rel
         if (la.key is None or la.step != self.step or la.last_stream is None or stream - la.last_stream != self.step
                 or la.key != self.key_for(stream, seed, st)):
-            return False
+            return None
         if self.pair is None:
             self.pair = (new_partials(self.device), new_partials(self.device))
         nws = self.pair[self.flip]
@@ -1790,330 +1785,318 @@ class _PowerAheadHook(PlanHook):
             nws = self.pair[self.flip]
         table[self.ws_slot] = la.partials.data_ptr()
         table[self.nws_slot] = nws.data_ptr()
-        self.now = (stream, seed, st, nws)
-        return True
+        return stream, seed, st, nws
 
-    def post_run(self, seed, base):
-        stream, seed, st, nws = self.now
+    def post_run(self, token):
+        stream, seed, st, nws = token
         la = self.la
         la.hits += 1
         la.key, la.partials, la.last_stream, la.last_delta = self.key_for((stream + self.step) & _M64, seed, st), nws, stream, self.step
         self.flip ^= 1
 
 
-class _PerlinAheadHook(PlanHook):
-    """A normalised Perlin call inside a plan, ONE launch per call in the steady state (``sonar_perlin_noise_ahead_f32``): the plan knows
-    the stream ids of the calls that follow (this call's + the streams a call takes), so a call's launch also runs the statistics pass
-    of the next call and the lattice of the call after it.  This hook keeps what earlier launches left -- three lattice buffers, two
-    statistics buffers per HIP stream, keyed by (seed, stream id) -- and supplies whatever is missing the ordinary way (a lattice launch;
-    ``have_stats`` = 0 makes the entry point launch the statistics pass): a reseed or a draw by somebody else costs one call its
-    shortcuts, never its values."""
+class _AheadHook(PlanHook):
+    """A look-ahead form a peephole put into a plan: the plan knows the stream ids of the calls that follow, so a call's launch also
+    computes data of a LATER call (statistics, a lattice) into ``BUFFERS`` (lattices, statistics buffers) kept per HIP stream, with a
+    "ready" map of what they hold, keyed by (seed, stream id).  ``pre_run`` fills the ``slots`` (``KEYS``, reserved by
+    ``_PlanBuilder.add_hook``) and returns (the stream's state, its ready map after the run).  A call that finds nothing (the first, after
+    a reseed, somebody else's draw or a call the entry point refused) loses its shortcut, never its values."""
 
-    KEYS = ("t_now", "p_now", "have", "t_next", "p_next", "t_out", "l_out")
+    KEYS = ()
+    BUFFERS = (0, 0)
 
-    def __init__(self, sa: int, la: int, count: int, lattice, device):
-        self.sa, self.la, self.count, self.lattice, self.device = sa, la, count, lattice, device  # lattice: (iters, C, H, W, blend)
-        self.managed = {}
-        self.by_stream = {}
-        self.now = None
+    def __init__(self, count: int, device, *, sa: int = 0, la: int = 0, lattice=None):
+        self.count, self.device = count, device  # count: the stream ids one call takes
+        self.sa, self.la, self.lattice = sa, la, lattice  # stream ids relative to the call's first; lattice: (iters, C, H, W, blend)
+        self.by_stream = {}  # hipStream_t -> [buffer addresses, ready map, buffers]
         self.hits = self.misses = 0
 
-    def bind(self, slot_of):
-        self.slot = {k: slot_of["perlin_" + k] for k in self.KEYS}
-
-    def pre_run(self, seed, base, table, st):
+    def _state(self, st: int):
         state = self.by_stream.get(st)
         if state is None:
-            _it, c, h, w, _bl = self.lattice
-            state = self.by_stream[st] = {"terms": [torch.empty((1, c, h, w), dtype=torch.float32, device=self.device) for _ in range(3)],
-                                          "parts": [new_partials(self.device) for _ in range(2)], "ready_terms": {}, "ready_parts": {}}
-            state["tptr"] = [t.data_ptr() for t in state["terms"]]  # (the addresses never change: one foreign call each, once)
-            state["pptr"] = [t.data_ptr() for t in state["parts"]]
-        terms, tptr, pptr = state["terms"], state["tptr"], state["pptr"]
-        l_now, s_now = (base + self.la) & _M64, (base + self.sa) & _M64
-        l_next, s_next, l_next2 = (l_now + self.count) & _M64, (s_now + self.count) & _M64, (l_now + 2 * self.count) & _M64
-        ti = state["ready_terms"].get((seed, l_now))
-        tn = state["ready_terms"].get((seed, l_next))
-        it, c, h, w, bl = self.lattice
-        if ti is None or tn is None:
-            # nobody left this call's lattice, or the next call's (the first run; after a reseed or somebody else's draw): the ordinary
-            # launch for whichever is missing, so that from the next call on every launch finds both its inputs
-            self.misses += 1
-            if ti is None:
-                ti = next(i for i in range(3) if i != tn)
-                _check(_lib.sonar_perlin_lattice_f32(terms[ti].data_ptr(), it, c, h, w, bl, seed, l_now, st), "sonar_perlin_lattice_f32")
-            if tn is None:
-                tn = next(i for i in range(3) if i != ti)
-                _check(_lib.sonar_perlin_lattice_f32(terms[tn].data_ptr(), it, c, h, w, bl, seed, l_next, st), "sonar_perlin_lattice_f32")
-        else:
-            self.hits += 1
-        pi = state["ready_parts"].get((seed, s_now))
-        have = pi is not None
-        if not have:
-            pi = 0
-        pn = 1 - pi
-        to = 3 - ti - tn  # the third of the buffers 0, 1, 2
-        target = l_next2
-        sl = self.slot
-        table[sl["t_now"]] = tptr[ti]
-        table[sl["p_now"]] = pptr[pi]
-        table[sl["have"]] = int(have)
-        table[sl["t_next"]] = tptr[tn]
-        table[sl["p_next"]] = pptr[pn]
-        table[sl["t_out"]] = tptr[to]
-        table[sl["l_out"]] = target
-        self.now = (state, {(seed, target): to, (seed, l_next): tn}, {(seed, s_next): pn})
-        # the launch overwrites a lattice buffer and a statistics buffer: until post_run says what they hold, nothing is "ready" -- a run
-        # that fails in between (an entry point refusing the call) must not leave keys pointing at overwritten buffers
-        state["ready_terms"], state["ready_parts"] = {}, {}
-        return True
+            bufs = [torch.empty((1, *self.lattice[1:4]), dtype=torch.float32, device=self.device) for _ in range(self.BUFFERS[0])]
+            bufs += [new_partials(self.device) for _ in range(self.BUFFERS[1])]
+            state = self.by_stream[st] = [[t.data_ptr() for t in bufs], {}, bufs]  # (the addresses never change: one foreign call each, once)
+        # the run overwrites buffers the map names: until post_run installs the token's map nothing is ready -- a run that fails in
+        # between (an entry point refusing the call) must not leave keys pointing at overwritten buffers
+        ready, state[1] = state[1], {}
+        return state, state[0], ready
 
-    def post_run(self, seed, base):
-        state, terms_ready, parts_ready = self.now
-        state["ready_terms"], state["ready_parts"] = terms_ready, parts_ready
+    def post_run(self, token):
+        state, ready = token
+        state[1] = ready
 
 
-def _peephole_perlin_ahead(records, b, rec):
-    """[sonar_perlin_lattice_f32 -> terms] [sonar_perlin_noise_f32(terms, ...)] of a traced step become one sonar_perlin_noise_ahead_f32
-    record driven by a ``_PerlinAheadHook`` -- where the entry point takes the shape (launch-bound sizes, whole tiles)."""
-    lib = load_raw()
-    out = []
-    i = 0
-    while i < len(records):
-        name, words, blob, patches = records[i]
-        nxt = records[i + 1] if i + 1 < len(records) else None
-        done = False
-        if name == "sonar_perlin_lattice_f32" and nxt is not None and nxt[0] == "sonar_perlin_noise_f32" and not blob and not nxt[2]:
-            lp = {pt.target: pt for pt in patches}
-            np_ = {pt.target: pt for pt in nxt[3]}
-            nw = nxt[1]
-            same_terms = (0 in lp and 0 in np_ and lp[0].source == PATCH_SLOT and np_[0].source == PATCH_SLOT and lp[0].index == np_[0].index
-                          and lp[0].addend == 0 and np_[0].addend == 0)
-            signed = lambda v: v - (1 << 64) if v >> 63 else v  # noqa: E731
-            B, chw, iters, offs = signed(nw[2]), signed(nw[3]), signed(nw[4]), signed(nw[8])
-            lat = tuple(signed(words[k]) for k in (1, 2, 3, 4, 5))  # iters, C, H, W, blend
-            if (same_terms and iters == 1 and lat[1] * lat[2] * lat[3] == chw and lib.sonar_perlin_noise_ahead_ok(B, chw, offs)
-                    and all(k in np_ for k in (1, 6, 7, 11)) and 7 in lp and lp[7].source == PATCH_STREAM and np_[7].source == PATCH_STREAM):
-                hook = _PerlinAheadHook(int(np_[7].addend), int(lp[7].addend), rec.count, lat, next(iter(b.temp_ranges))[2].device)
-                slots = {}
-                for key in hook.KEYS:
-                    slots[key] = b.slot_of[("hook", "perlin_" + key)] = len(b.slots)
-                    b.slots.append(None)
-                w2 = [0, 0, nw[2], nw[3], nw[5], 0, 0, nw[8], nw[9], nw[10], 0, 0, 0, 0, 0, 0, words[1], words[2], words[3], words[4], words[5], 0, 0]
-                p2 = [PlanPatch(PATCH_SLOT, 0, slots["t_now"], 8, 0), PlanPatch(PATCH_SLOT, 1, np_[1].index, 8, np_[1].addend),
-                      PlanPatch(PATCH_SEED, 5, 0, 8, 0), PlanPatch(PATCH_STREAM, 6, 0, 8, np_[7].addend),
-                      PlanPatch(PATCH_SLOT, 10, slots["p_now"], 8, 0), PlanPatch(PATCH_SLOT, 11, slots["have"], 8, 0),
-                      PlanPatch(PATCH_STREAM, 12, 0, 8, np_[7].addend + rec.count), PlanPatch(PATCH_SLOT, 13, slots["t_next"], 8, 0),
-                      PlanPatch(PATCH_SLOT, 14, slots["p_next"], 8, 0), PlanPatch(PATCH_SLOT, 15, slots["t_out"], 8, 0),
-                      PlanPatch(PATCH_SLOT, 21, slots["l_out"], 8, 0)]
-                out.append(("sonar_perlin_noise_ahead_f32", w2, b"", p2))
-                rec.hooks.append(hook)
-                i += 2
-                done = True
-        if not done:
-            out.append(records[i])
-            i += 1
-    return out
-
-
-class _FillAheadHook(PlanHook):
-    """A normalised uniform / Gaussian fill (``sonar_philox_noise_ahead_f32``) or pyramid call (``sonar_pyramid_noise_ahead_f32``) inside a
-    plan, round 6: the plan knows the stream ids of the call that follows, so this call's launch also computes that call's statistics
-    -- the fill in the same waves, behind the stores of the final pass; the pyramid in workgroups of their own.  Two statistics buffers
-    per HIP stream, keyed by (seed, stream id); a call that finds nothing (the first, after a reseed, somebody else's draw or a call
-    the entry point refused) gets ``have_stats`` = 0 and the entry point computes the statistics first: it loses its shortcut, never
-    its values."""
+class _FillAheadHook(_AheadHook):
+    """A normalised uniform / Gaussian fill (``sonar_philox_noise_ahead_f32``) or pyramid call (``sonar_pyramid_noise_ahead_f32``): the
+    call's launch also computes the next call's statistics -- the fill in the same waves, behind the stores of the final pass; the
+    pyramid in workgroups of their own.  A call that finds none gets ``have_stats`` = 0: the entry point computes them first."""
 
     KEYS = ("p_now", "have", "p_next")
-
-    def __init__(self, tag: str, sa: int, count: int, device):
-        self.tag, self.sa, self.count, self.device = tag, sa, count, device
-        self.managed = {}
-        self.by_stream = {}
-        self.now = None
-        self.hits = self.misses = 0
-
-    def bind(self, slot_of):
-        self.slot = {k: slot_of[self.tag + k] for k in self.KEYS}
+    BUFFERS = (0, 2)
 
     def pre_run(self, seed, base, table, st):
-        state = self.by_stream.get(st)
-        if state is None:
-            state = self.by_stream[st] = {"parts": [new_partials(self.device) for _ in range(2)], "ready": {}}
+        state, ptr, ready = self._state(st)
         s_now = (base + self.sa) & _M64
-        s_next = (s_now + self.count) & _M64
-        pi = state["ready"].get((seed, s_now))
+        pi = ready.get((seed, s_now))
         have = pi is not None
         if have:
             self.hits += 1
         else:
             self.misses += 1
             pi = 0
-        sl = self.slot
-        table[sl["p_now"]] = state["parts"][pi].data_ptr()
-        table[sl["have"]] = int(have)
-        table[sl["p_next"]] = state["parts"][1 - pi].data_ptr()
-        self.now = (state, {(seed, s_next): 1 - pi})
-        state["ready"] = {}  # (as in _PerlinAheadHook: valid again in post_run)
-        return True
-
-    def post_run(self, seed, base):
-        self.now[0]["ready"] = self.now[1]
+        p_now, have_stats, p_next = self.slots
+        table[p_now] = ptr[pi]
+        table[have_stats] = int(have)
+        table[p_next] = ptr[1 - pi]
+        return state, {(seed, (s_now + self.count) & _M64): 1 - pi}
 
 
-def _peephole_fill_ahead(records, b, rec):
+class _LatticeAheadHook(_AheadHook):
+    """A chain whose Perlin item is hosted by the pyramid kernel: the plane kernel's launch of call n computes the lattice of call n + 1 in
+    extra workgroups (``sonar_pyramid_generate_acc_ahead_f32``).  A call that finds none launches its lattice the ordinary way."""
+
+    KEYS = ("t_now", "t_out", "l_out")
+    BUFFERS = (2, 0)
+
+    def pre_run(self, seed, base, table, st):
+        state, ptr, ready = self._state(st)
+        l_now = (base + self.la) & _M64
+        l_next = (l_now + self.count) & _M64
+        ti = ready.get((seed, l_now))
+        if ti is None:
+            ti = 0
+            _check(_lib.sonar_perlin_lattice_f32(ptr[ti], *self.lattice, seed, l_now, st), "sonar_perlin_lattice_f32")
+            self.misses += 1
+        else:
+            self.hits += 1
+        t_now, t_out, l_out = self.slots
+        table[t_now] = ptr[ti]
+        table[t_out] = ptr[1 - ti]
+        table[l_out] = l_next
+        return state, {(seed, l_next): 1 - ti}
+
+
+class _PerlinAheadHook(_AheadHook):
+    """A normalised Perlin call, ONE launch per call in the steady state (``sonar_perlin_noise_ahead_f32``): a call's launch also runs the
+    statistics pass of the next call and the lattice of the call after it.  Buffers 0-2 are lattices, ready under ("t", seed, stream id),
+    3-4 statistics, under ("p", seed, stream id); whatever is missing is supplied the ordinary way (a lattice launch; ``have_stats`` = 0
+    makes the entry point launch the statistics pass)."""
+
+    KEYS = ("t_now", "p_now", "have", "t_next", "p_next", "t_out", "l_out")
+    BUFFERS = (3, 2)
+
+    def pre_run(self, seed, base, table, st):
+        state, ptr, ready = self._state(st)
+        count = self.count
+        l_now, s_now = (base + self.la) & _M64, (base + self.sa) & _M64
+        l_next = (l_now + count) & _M64
+        ti = ready.get(("t", seed, l_now))
+        tn = ready.get(("t", seed, l_next))
+        if ti is None or tn is None:
+            # nobody left this call's lattice, or the next call's (the first run; after a reseed or somebody else's draw): the ordinary
+            # launch for whichever is missing, so that from the next call on every launch finds both its inputs
+            self.misses += 1
+            if ti is None:
+                ti = next(i for i in range(3) if i != tn)
+                _check(_lib.sonar_perlin_lattice_f32(ptr[ti], *self.lattice, seed, l_now, st), "sonar_perlin_lattice_f32")
+            if tn is None:
+                tn = next(i for i in range(3) if i != ti)
+                _check(_lib.sonar_perlin_lattice_f32(ptr[tn], *self.lattice, seed, l_next, st), "sonar_perlin_lattice_f32")
+        else:
+            self.hits += 1
+        pi = ready.get(("p", seed, s_now))
+        have = pi is not None
+        pi = pi if have else 0
+        to = 3 - ti - tn  # the third of the lattice buffers
+        l_out = (l_now + 2 * count) & _M64
+        t_now, p_now, have_stats, t_next, p_next, t_out, l_out_slot = self.slots
+        table[t_now] = ptr[ti]
+        table[p_now] = ptr[3 + pi]
+        table[have_stats] = int(have)
+        table[t_next] = ptr[tn]
+        table[p_next] = ptr[4 - pi]
+        table[t_out] = ptr[to]
+        table[l_out_slot] = l_out
+        return state, {("t", seed, l_out): to, ("t", seed, l_next): tn, ("p", seed, (s_now + count) & _M64): 1 - pi}
+
+
+# The parameters of the entry points the peepholes below read or write (include/sonar_hip.h; tests/test_plan_cpu.py holds the two to
+# each other): the rewrites address arguments by these names, never by position.
+_PARAMS = {name: tuple(params.split()) for name, params in (
+    ("sonar_philox_noise_f32", "uniform out n seed stream_id elem_offset sub mul add factor threshold_std_devs partials stream"),
+    ("sonar_philox_noise_ahead_f32", "uniform out n seed stream_id elem_offset sub mul add factor threshold_std_devs partials have_stats "
+        "next_stream_id partials_next stream"),
+    ("sonar_perlin_lattice_f32", "terms_sum iters C H W blend_mode seed stream_id stream"),
+    ("sonar_perlin_noise_f32", "terms out B chw iters div_fac seed stream_id elem_offset factor threshold_std_devs partials stream"),
+    ("sonar_perlin_noise_ahead_f32", "terms out B chw div_fac seed stream_id elem_offset factor threshold_std_devs partials have_stats "
+        "next_stream_id terms_next partials_next lattice_out lattice_iters C H W blend_mode lattice_stream_id stream"),
+    ("sonar_pyramid_noise_f32", "out planes H W nlevels level_ptrs level_h level_w level_weight mode seed stream_id elem_offset factor "
+        "threshold_std_devs partials stream"),
+    ("sonar_pyramid_noise_ahead_f32", "out planes H W nlevels level_h level_w level_weight mode seed stream_id elem_offset factor "
+        "threshold_std_devs partials have_stats next_stream_id next_nlevels next_level_h next_level_w next_level_weight partials_next stream"),
+    ("sonar_pyramid_generate_acc_f32", "acc pre planes H W nlevels level_ptrs level_h level_w level_weight mode seed stream_id elem_offset stream"),
+    ("sonar_pyramid_generate_acc_ahead_f32", "acc pre planes H W nlevels level_ptrs level_h level_w level_weight mode seed stream_id elem_offset "
+        "lattice_out lattice_iters lattice_channels blend_mode lattice_stream_id stream"))}
+
+
+def _signed(word: int) -> int:
+    return word - (1 << 64) if word >> 63 else word
+
+
+def _patch(source: int, index: int = 0, addend: int = 0) -> PlanPatch:
+    return PlanPatch(source, 0, index, 8, addend)  # (the target: wherever _new_record places it)
+
+
+def _args(record):
+    """A record's arguments by name: ({parameter: word}, {parameter: patch}); patches into the blob belong to no parameter."""
+    params = _PARAMS[record[0]]
+    return dict(zip(params, record[1])), {params[pt.target]: pt for pt in record[3] if pt.target >= 0}
+
+
+def _new_record(name: str, spec: dict, source=None, blob: bytes = b""):
+    """A ``name`` record from {parameter: value}: a PlanPatch is placed at the parameter (word 0), anything else is the word.  A
+    ``source`` record's words and patches for parameters of the same names that ``spec`` leaves alone are taken over first (patches in
+    their order, those into the blob as they are); then the spec's patches, in parameter order.  Parameters nothing sets are 0."""
+    params = _PARAMS[name]
+    words, patches = [0] * len(params), []
+    if source is not None:
+        src = _PARAMS[source[0]]
+        given = dict(zip(src, source[1]))
+        words = [given.get(p, 0) for p in params]
+        for pt in source[3]:
+            p = src[pt.target] if pt.target >= 0 else None
+            if p is None or (p in params and p not in spec):
+                patches.append(pt if p is None else PlanPatch(pt.source, params.index(p), pt.index, pt.width, pt.addend))
+    for i, p in enumerate(params):
+        value = spec.get(p)
+        if isinstance(value, PlanPatch):
+            words[i] = 0
+            patches.append(PlanPatch(value.source, i, value.index, value.width, value.addend))
+        elif value is not None:
+            words[i] = value
+    return name, words, blob, patches
+
+
+def _peephole_perlin_ahead(records, b):
+    """[sonar_perlin_lattice_f32 -> terms] [sonar_perlin_noise_f32(terms, ...)] of a traced step become one sonar_perlin_noise_ahead_f32
+    record driven by a ``_PerlinAheadHook`` -- where the entry point takes the shape (launch-bound sizes, whole tiles)."""
+    lib = load_raw()
+    count = b.rec.count
+    out = []
+    i = 0
+    while i < len(records):
+        lat_rec, nxt = records[i], records[i + 1] if i + 1 < len(records) else None
+        if lat_rec[0] == "sonar_perlin_lattice_f32" and nxt is not None and nxt[0] == "sonar_perlin_noise_f32" and not lat_rec[2] and not nxt[2]:
+            (lw, lpt), (nw, npt) = _args(lat_rec), _args(nxt)
+            lt, nt = lpt.get("terms_sum"), npt.get("terms")
+            same_terms = (lt is not None and nt is not None
+                          and (lt.source, lt.index, lt.addend) == (nt.source, nt.index, nt.addend) == (PATCH_SLOT, lt.index, 0))
+            lat = tuple(_signed(lw[p]) for p in ("iters", "C", "H", "W", "blend_mode"))
+            chw = _signed(nw["chw"])
+            if (same_terms and _signed(nw["iters"]) == 1 and lat[1] * lat[2] * lat[3] == chw
+                    and lib.sonar_perlin_noise_ahead_ok(_signed(nw["B"]), chw, _signed(nw["elem_offset"]))
+                    and all(p in npt for p in ("out", "seed", "stream_id", "partials")) and "stream_id" in lpt
+                    and lpt["stream_id"].source == PATCH_STREAM and npt["stream_id"].source == PATCH_STREAM):
+                stream = npt["stream_id"]
+                hook = _PerlinAheadHook(count, b.device, sa=int(stream.addend), la=int(lpt["stream_id"].addend), lattice=lat)
+                s = {k: _patch(PATCH_SLOT, slot) for k, slot in b.add_hook(hook).items()}
+                out.append(_new_record("sonar_perlin_noise_ahead_f32", {
+                    "terms": s["t_now"], "out": npt["out"], "B": nw["B"], "chw": nw["chw"], "div_fac": nw["div_fac"], "seed": npt["seed"],
+                    "stream_id": stream, "elem_offset": nw["elem_offset"], "factor": nw["factor"], "threshold_std_devs": nw["threshold_std_devs"],
+                    "partials": s["p_now"], "have_stats": s["have"], "next_stream_id": _patch(PATCH_STREAM, addend=stream.addend + count),
+                    "terms_next": s["t_next"], "partials_next": s["p_next"], "lattice_out": s["t_out"], "lattice_iters": lw["iters"], "C": lw["C"],
+                    "H": lw["H"], "W": lw["W"], "blend_mode": lw["blend_mode"], "lattice_stream_id": s["l_out"]}))
+                i += 2
+                continue
+        out.append(lat_rec)
+        i += 1
+    return out
+
+
+def _peephole_fill_ahead(records, b):
     """Every [sonar_philox_noise_f32] record of a traced step whose shape has a statistics pass (uniform draws, or factor != 1) becomes a
     sonar_philox_noise_ahead_f32 record driven by a ``_FillAheadHook``."""
     lib = load_raw()
     out = []
-    signed = lambda v: v - (1 << 64) if v >> 63 else v  # noqa: E731
-    for k, (name, words, blob, patches) in enumerate(records):
-        if name == "sonar_philox_noise_f32" and not blob:
-            pt = {p.target: p for p in patches}
-            factor = C.c_float.from_buffer_copy(int(words[9] & 0xFFFFFFFF).to_bytes(4, "little")).value
-            if (all(t in pt for t in (1, 3, 4, 11)) and pt[3].source == PATCH_SEED and pt[4].source == PATCH_STREAM
-                    and lib.sonar_philox_noise_ahead_ok(int(signed(words[0])), signed(words[2]), factor)):
-                tag = f"fill{k}_"
-                hook = _FillAheadHook(tag, int(pt[4].addend), rec.count, next(iter(b.temp_ranges))[2].device)
-                slots = {}
-                for key in hook.KEYS:
-                    slots[key] = b.slot_of[("hook", tag + key)] = len(b.slots)
-                    b.slots.append(None)
-                w2 = list(words[:11]) + [0, 0, 0, 0, 0]
-                p2 = [pt[1], pt[3], pt[4], PlanPatch(PATCH_SLOT, 11, slots["p_now"], 8, 0), PlanPatch(PATCH_SLOT, 12, slots["have"], 8, 0),
-                      PlanPatch(PATCH_STREAM, 13, 0, 8, pt[4].addend + rec.count), PlanPatch(PATCH_SLOT, 14, slots["p_next"], 8, 0)]
-                out.append(("sonar_philox_noise_ahead_f32", w2, b"", p2))
-                rec.hooks.append(hook)
-                continue
-        out.append((name, words, blob, patches))
+    for r in records:
+        if r[0] == "sonar_philox_noise_f32" and not r[2]:
+            w, pt = _args(r)
+            factor = C.c_float.from_buffer_copy(int(w["factor"] & 0xFFFFFFFF).to_bytes(4, "little")).value
+            if (all(p in pt for p in ("out", "seed", "stream_id", "partials")) and pt["seed"].source == PATCH_SEED
+                    and pt["stream_id"].source == PATCH_STREAM and lib.sonar_philox_noise_ahead_ok(_signed(w["uniform"]), _signed(w["n"]), factor)):
+                stream = pt["stream_id"]
+                hook = _FillAheadHook(b.rec.count, b.device, sa=int(stream.addend))
+                s = {k: _patch(PATCH_SLOT, slot) for k, slot in b.add_hook(hook).items()}
+                r = _new_record("sonar_philox_noise_ahead_f32", {"partials": s["p_now"], "have_stats": s["have"], "partials_next": s["p_next"],
+                                                                 "next_stream_id": _patch(PATCH_STREAM, addend=stream.addend + b.rec.count)}, r)
+        out.append(r)
     return out
 
 
-def _peephole_pyramid_ahead(records, b, rec):
+def _peephole_pyramid_ahead(records, b):
     """A [sonar_pyramid_noise_f32] record of a traced step whose levels are all drawn in the kernel (a level rule: PATCH_LEVELS) with the
     bilinear mode becomes a sonar_pyramid_noise_ahead_f32 record: a second level rule -- the next call's, its stream ids ``rec.count``
     further on -- joins the blob, a ``_FillAheadHook`` supplies the two statistics buffers."""
+    count = b.rec.count
     out = []
-    for k, (name, words, blob, patches) in enumerate(records):
-        done = False
-        if name == "sonar_pyramid_noise_f32" and blob:
-            pt = {p.target: p for p in patches}
-            lev = pt.get(4)
-            if (lev is not None and lev.source == PATCH_LEVELS and all(t in pt for t in (0, 6, 7, 8, 10, 11, 15)) and pt[10].source == PATCH_SEED
-                    and pt[11].source == PATCH_STREAM and all(pt[t].source == PATCH_BLOB for t in (6, 7, 8)) and int(words[9]) == 0):
-                rule = PlanLevels.from_buffer_copy(bytes(blob[lev.index:lev.index + C.sizeof(PlanLevels)]))
+    for r in records:
+        if r[0] == "sonar_pyramid_noise_f32" and r[2]:
+            w, pt = _args(r)
+            lev, table = pt.get("nlevels"), ("level_h", "level_w", "level_weight")
+            if (lev is not None and lev.source == PATCH_LEVELS and all(p in pt for p in ("out", *table, "seed", "stream_id", "partials"))
+                    and pt["seed"].source == PATCH_SEED and pt["stream_id"].source == PATCH_STREAM
+                    and all(pt[p].source == PATCH_BLOB for p in table) and int(w["mode"]) == 0):
+                rule = PlanLevels.from_buffer_copy(bytes(r[2][lev.index:lev.index + C.sizeof(PlanLevels)]))
                 n = max(int(rule.iterations), 1)
-                blob2 = bytearray(blob)
-                h_off = _blob_reserve(blob2, 8 * n, bytes(8 * n))
-                w_off = _blob_reserve(blob2, 8 * n, bytes(8 * n))
-                wt_off = _blob_reserve(blob2, 4 * n, bytes(4 * n))
-                rule_off = _blob_reserve(blob2, C.sizeof(PlanLevels),
+                blob = bytearray(r[2])
+                h_off, w_off, wt_off = (_blob_reserve(blob, size * n, b"") for size in (8, 8, 4))
+                rule_off = _blob_reserve(blob, C.sizeof(PlanLevels),
                                          bytes(PlanLevels(rule.H, rule.W, rule.discount, rule.iterations, 0, h_off, w_off, wt_off)))
-                tag = f"pyr{k}_"
-                hook = _FillAheadHook(tag, int(pt[11].addend), rec.count, next(iter(b.temp_ranges))[2].device)
-                slots = {}
-                for key in hook.KEYS:
-                    slots[key] = b.slot_of[("hook", tag + key)] = len(b.slots)
-                    b.slots.append(None)
-                w2 = [0, words[1], words[2], words[3], 0, 0, 0, 0, words[9], 0, 0, words[12], words[13], words[14], 0, 0, 0, 0, 0, 0, 0, 0, 0]
-                p2 = [PlanPatch(PATCH_SLOT, 0, pt[0].index, 8, pt[0].addend), PlanPatch(PATCH_LEVELS, 4, lev.index, 8, lev.addend),
-                      PlanPatch(PATCH_BLOB, 5, 0, 8, pt[6].addend), PlanPatch(PATCH_BLOB, 6, 0, 8, pt[7].addend), PlanPatch(PATCH_BLOB, 7, 0, 8, pt[8].addend),
-                      PlanPatch(PATCH_SEED, 9, 0, 8, 0), PlanPatch(PATCH_STREAM, 10, 0, 8, pt[11].addend),
-                      PlanPatch(PATCH_SLOT, 14, slots["p_now"], 8, 0), PlanPatch(PATCH_SLOT, 15, slots["have"], 8, 0),
-                      PlanPatch(PATCH_STREAM, 16, 0, 8, pt[11].addend + rec.count), PlanPatch(PATCH_LEVELS, 17, rule_off, 8, lev.addend + rec.count),
-                      PlanPatch(PATCH_BLOB, 18, 0, 8, h_off), PlanPatch(PATCH_BLOB, 19, 0, 8, w_off), PlanPatch(PATCH_BLOB, 20, 0, 8, wt_off),
-                      PlanPatch(PATCH_SLOT, 21, slots["p_next"], 8, 0)]
-                out.append(("sonar_pyramid_noise_ahead_f32", w2, bytes(blob2), p2))
-                rec.hooks.append(hook)
-                done = True
-        if not done:
-            out.append((name, words, blob, patches))
+                stream = pt["stream_id"]
+                hook = _FillAheadHook(count, b.device, sa=int(stream.addend))
+                s = {k: _patch(PATCH_SLOT, slot) for k, slot in b.add_hook(hook).items()}
+                r = _new_record("sonar_pyramid_noise_ahead_f32", {
+                    **{p: w[p] for p in ("planes", "H", "W", "mode", "elem_offset", "factor", "threshold_std_devs")},
+                    **{p: pt[p] for p in ("out", *table, "seed", "stream_id")}, "nlevels": lev, "partials": s["p_now"], "have_stats": s["have"],
+                    "next_stream_id": _patch(PATCH_STREAM, addend=stream.addend + count), "partials_next": s["p_next"],
+                    "next_nlevels": _patch(PATCH_LEVELS, rule_off, lev.addend + count), "next_level_h": _patch(PATCH_BLOB, addend=h_off),
+                    "next_level_w": _patch(PATCH_BLOB, addend=w_off), "next_level_weight": _patch(PATCH_BLOB, addend=wt_off)}, blob=bytes(blob))
+        out.append(r)
     return out
 
 
-class _LatticeAheadHook(PlanHook):
-    """A chain whose Perlin item is hosted by the pyramid kernel, inside a plan: the lattice launch leaves the call's critical path --
-    the plane kernel's launch of call n computes the lattice of call n + 1 in extra workgroups (``sonar_pyramid_generate_acc_ahead_f32``).
-    Two buffers per HIP stream, keyed by (seed, stream id); a call that finds nothing (the first, or after a reseed) launches its lattice
-    the ordinary way."""
-
-    KEYS = ("t_now", "t_out", "l_out")
-
-    def __init__(self, la: int, count: int, lattice, device):
-        self.la, self.count, self.lattice, self.device = la, count, lattice, device  # lattice: (iters, C, H, W, blend)
-        self.managed = {}
-        self.by_stream = {}
-        self.now = None
-        self.hits = self.misses = 0
-
-    def bind(self, slot_of):
-        self.slot = {k: slot_of["lattice_" + k] for k in self.KEYS}
-
-    def pre_run(self, seed, base, table, st):
-        it, c, h, w, bl = self.lattice
-        state = self.by_stream.get(st)
-        if state is None:
-            state = self.by_stream[st] = {"terms": [torch.empty((1, c, h, w), dtype=torch.float32, device=self.device) for _ in range(2)], "ready": {}}
-        terms = state["terms"]
-        l_now = (base + self.la) & _M64
-        l_next = (l_now + self.count) & _M64
-        ti = state["ready"].get((seed, l_now))
-        if ti is None:
-            ti = 0
-            _check(_lib.sonar_perlin_lattice_f32(terms[ti].data_ptr(), it, c, h, w, bl, seed, l_now, st), "sonar_perlin_lattice_f32")
-            self.misses += 1
-        else:
-            self.hits += 1
-        sl = self.slot
-        table[sl["t_now"]] = terms[ti].data_ptr()
-        table[sl["t_out"]] = terms[1 - ti].data_ptr()
-        table[sl["l_out"]] = l_next
-        self.now = (state, {(seed, l_next): 1 - ti})
-        state["ready"] = {}  # (as in _PerlinAheadHook: valid again in post_run)
-        return True
-
-    def post_run(self, seed, base):
-        self.now[0]["ready"] = self.now[1]
-
-
-def _peephole_lattice_ahead(records, b, rec):
+def _peephole_lattice_ahead(records, b):
     """[sonar_perlin_lattice_f32 -> terms] ... [sonar_pyramid_generate_acc_f32(pre = Perlin prefix over those terms)] of a traced chain step:
     the lattice record goes, the plane kernel's record becomes sonar_pyramid_generate_acc_ahead_f32 driven by a ``_LatticeAheadHook``."""
-    signed = lambda v: v - (1 << 64) if v >> 63 else v  # noqa: E731
-    terms_off = FoldPrefixArg.terms.offset
-    for i, (name, words, blob, patches) in enumerate(records):
-        if name != "sonar_perlin_lattice_f32" or blob:
+    for i, r in enumerate(records):
+        if r[0] != "sonar_perlin_lattice_f32" or r[2]:
             continue
-        lp = {pt.target: pt for pt in patches}
-        if 0 not in lp or lp[0].source != PATCH_SLOT or 7 not in lp or lp[7].source != PATCH_STREAM:
+        lw, lpt = _args(r)
+        terms, stream = lpt.get("terms_sum"), lpt.get("stream_id")
+        if terms is None or terms.source != PATCH_SLOT or stream is None or stream.source != PATCH_STREAM:
             continue
-        tslot = lp[0].index
-        users = [j for j, r in enumerate(records) if j != i and any(pt.source == PATCH_SLOT and pt.index == tslot for pt in r[3])]
+        users = [j for j, u in enumerate(records) if j != i and any(pt.source == PATCH_SLOT and pt.index == terms.index for pt in u[3])]
         if len(users) != 1 or records[users[0]][0] != "sonar_pyramid_generate_acc_f32" or users[0] < i:
             continue
-        j = users[0]
-        _n, w2, blob2, p2 = records[j]
-        pre_arg = next((pt for pt in p2 if pt.source == PATCH_BLOB and pt.target == 1), None)
-        if pre_arg is None:
+        j, acc = users[0], records[users[0]]
+        aw, apt = _args(acc)
+        pre = apt.get("pre")
+        if pre is None or pre.source != PATCH_BLOB:
             continue
-        field = -(int(pre_arg.addend) + terms_off + 1)  # the blob patch that fills pre.terms
-        tpatch = next((pt for pt in p2 if pt.source == PATCH_SLOT and pt.index == tslot and pt.target == field and pt.addend == 0), None)
-        lat = tuple(signed(words[k]) for k in (1, 2, 3, 4, 5))  # iters, C, H, W, blend
-        if tpatch is None or (signed(w2[3]), signed(w2[4])) != (lat[2], lat[3]):
+        field = -(int(pre.addend) + FoldPrefixArg.terms.offset + 1)  # the blob patch that fills pre.terms
+        tpatch = next((pt for pt in acc[3] if pt.source == PATCH_SLOT and pt.index == terms.index and pt.target == field and pt.addend == 0), None)
+        lat = tuple(_signed(lw[p]) for p in ("iters", "C", "H", "W", "blend_mode"))
+        if tpatch is None or (aw["H"], aw["W"]) != (lw["H"], lw["W"]):
             continue
-        hook = _LatticeAheadHook(int(lp[7].addend), rec.count, lat, next(iter(b.temp_ranges))[2].device)
-        slots = {}
-        for key in hook.KEYS:
-            slots[key] = b.slot_of[("hook", "lattice_" + key)] = len(b.slots)
-            b.slots.append(None)
-        new_patches = [PlanPatch(PATCH_SLOT, field, slots["t_now"], 8, 0) if pt is tpatch else pt for pt in p2]
-        new_patches += [PlanPatch(PATCH_SLOT, 14, slots["t_out"], 8, 0), PlanPatch(PATCH_SLOT, 18, slots["l_out"], 8, 0)]
-        new_words = list(w2[:14]) + [0, words[1], words[2], words[5], 0, 0]
+        s = b.add_hook(_LatticeAheadHook(b.rec.count, b.device, la=int(stream.addend), lattice=lat))
+        source = acc[:3] + ([PlanPatch(PATCH_SLOT, field, s["t_now"], 8, 0) if pt is tpatch else pt for pt in acc[3]],)
         out = list(records)
-        out[j] = ("sonar_pyramid_generate_acc_ahead_f32", new_words, blob2, new_patches)
+        out[j] = _new_record("sonar_pyramid_generate_acc_ahead_f32", {
+            "lattice_out": _patch(PATCH_SLOT, s["t_out"]), "lattice_iters": lw["iters"], "lattice_channels": lw["C"], "blend_mode": lw["blend_mode"],
+            "lattice_stream_id": _patch(PATCH_SLOT, s["l_out"])}, source, blob=acc[2])
         del out[i]
-        rec.hooks.append(hook)
-        return _peephole_lattice_ahead(out, b, rec)
+        return _peephole_lattice_ahead(out, b)
     return records
 
 
@@ -2128,7 +2111,7 @@ def _double_word(v: float) -> int:
 class _PlanBuilder:
     """Turns a recorded call into a ``sonar_plan`` + the Python-side description of its slots and result."""
 
-    def __init__(self, rec: _Recorder, result):
+    def __init__(self, rec: _Recorder):
         self.rec = rec
         self.slots = []      # [tensor template] in slot order
         self.slot_of = {}    # id(tensor) or hook key -> slot index
@@ -2137,7 +2120,7 @@ class _PlanBuilder:
         for h in rec.hooks:
             self.managed.update(h.managed)
         self.temp_ranges = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), t) for t in rec.temps if t.numel()]
-        self.result = result
+        self.device = self.temp_ranges[0][2].device if self.temp_ranges else torch.device("cuda", torch.cuda.current_device())
         self.scratch_refs = []  # weak references to the temporaries the plan will own copies of
 
     def resolve(self, addr: int):
@@ -2164,6 +2147,13 @@ class _PlanBuilder:
             raise PlanError(f"address {addr:#x} belongs to no tensor the trace knows")
         self.constants.append(t)
         return None
+
+    def add_hook(self, hook: "_AheadHook") -> dict:
+        """Reserve the slots ``hook.KEYS`` name (filled per call by its pre_run), register the hook with the recording: {key: slot}."""
+        hook.slots = tuple(range(len(self.slots), len(self.slots) + len(hook.KEYS)))
+        self.slots += [None] * len(hook.KEYS)
+        self.rec.hooks.append(hook)
+        return dict(zip(hook.KEYS, hook.slots))
 
     def stream_addend(self, value: int) -> int:
         if self.rec.base is None or value < self.rec.base or value - self.rec.base > self.rec.count + 64:
@@ -2270,7 +2260,8 @@ def _blob_reserve(blob: bytearray, size: int, data: bytes) -> int:
 
 class Plan:
     """A recorded step (``sonar_plan``) with what the host must supply per call: fresh tensors for everything the result owns, the
-    plan's own scratch tensors (one set per HIP stream), the RNG position, and the hooks' values."""
+    plan's own scratch tensors (one set per HIP stream), the RNG position, and the hooks' values.  Calls on one plan must be serialised
+    by the caller, as ``Planned`` does: the hooks' buffers are shared per HIP stream."""
 
     def __init__(self, handle, nslots, fresh, scratch, result_spec, constants, rec: _Recorder, take, rewind, guards, device):
         self.handle, self.nslots = handle, nslots
@@ -2313,11 +2304,14 @@ class Plan:
         table = self._table(st)
         seed, base = self.take(self.rng_count) if self.rng_count else (0, 0)
         seed &= _M64
+        tokens = []
         for h in self.hooks:
-            if not h.pre_run(seed, base, table, st):
+            token = h.pre_run(seed, base, table, st)
+            if token is None:
                 if self.rng_count:
                     self.rewind(base, self.rng_count)
                 return NOT_RUN
+            tokens.append(token)
         fresh = []
         device = self.device
         for slot, shape, dtype in self.fresh:
@@ -2333,8 +2327,8 @@ class Plan:
             if rc == ERR_UNSUPPORTED:
                 return NOT_RUN  # an entry point refused this call's values (e.g. a level table the plane kernel cannot hold): ordinary path
             _check(rc, f"sonar_plan_run (record {self.failed.value})")
-        for h in self.hooks:
-            h.post_run(seed, base)
+        for h, token in zip(self.hooks, tokens):
+            h.post_run(token)
         self.runs += 1
         return _rebuild(self.result_spec, fresh)
 
@@ -2440,17 +2434,19 @@ trace_plan.last_reason = None
 def _build_plan(rec: _Recorder, result, take, rewind, guards) -> Plan:
     if not rec.calls:
         raise PlanError("the call launched nothing")
-    b = _PlanBuilder(rec, result)
+    b = _PlanBuilder(rec)
     records = [b.record(name, args) for name, args in rec.calls]
     # the tensors the entry points were handed are known now (constants are kept by the builder): let go of them, so that the only
     # holders of a temporary's storage left are this trace's own note of the allocation -- and whoever else kept it (checked below)
     rec.seen.clear()
     if PERLIN_AHEAD:
-        records = _peephole_lattice_ahead(_peephole_perlin_ahead(records, b, rec), b, rec)
+        records = _peephole_lattice_ahead(_peephole_perlin_ahead(records, b), b)
     if FILL_AHEAD:
-        records = _peephole_fill_ahead(records, b, rec)
+        records = _peephole_fill_ahead(records, b)
     if PYRAMID_AHEAD:
-        records = _peephole_pyramid_ahead(records, b, rec)
+        records = _peephole_pyramid_ahead(records, b)
+    # the slots a record reads: an operand a rewrite dropped (statistics partials, a lattice) keeps its slot number but gets no scratch
+    read = {pt.index for _n, _w, _b, patches in records for pt in patches if pt.source == PATCH_SLOT}
     # what the result owns must be fresh per call: the tensors handed back and the statistics partials tagged onto them
     owned = {}  # id(temp) -> index in the fresh list
 
@@ -2484,7 +2480,7 @@ def _build_plan(rec: _Recorder, result, take, rewind, guards) -> Plan:
     by_id = {id(t): t for _lo, _hi, t in b.temp_ranges}
     for tid, idx in owned.items():
         t = by_id[tid]
-        if tid not in b.slot_of:  # a result no kernel wrote?  (cannot happen on a device path)
+        if b.slot_of.get(tid) not in read:  # a result no kernel wrote?  (cannot happen on a device path)
             raise PlanError("a result tensor that no entry point was handed")
         fresh[idx] = (b.slot_of[tid], tuple(t.shape), t.dtype)
     hook_slots = {}
@@ -2497,11 +2493,11 @@ def _build_plan(rec: _Recorder, result, take, rewind, guards) -> Plan:
             # every live tensor on its storage shows in the storage's use count (2 = the trace's own note + the handle asked for here)
             if torch._C._storage_Use_Count(t.untyped_storage()._cdata) > 2:
                 raise PlanError("a tensor allocated during the call outlives it")
-            scratch.append((slot, tuple(t.shape), t.dtype))
+            if slot in read:
+                scratch.append((slot, tuple(t.shape), t.dtype))
             b.scratch_refs.append(weakref.ref(t))
     for h in rec.hooks:
         h.bind(hook_slots)
-    device = next(iter(by_id.values())).device if by_id else torch.device("cuda", torch.cuda.current_device())
     lib = load_raw()
     nslots = len(b.slots)
     handle = lib.sonar_plan_create(nslots)
@@ -2519,7 +2515,7 @@ def _build_plan(rec: _Recorder, result, take, rewind, guards) -> Plan:
     except Exception:
         lib.sonar_plan_destroy(handle)
         raise
-    plan = Plan(handle, nslots, fresh, scratch, result_spec, b.constants, rec, take, rewind, guards, device)
+    plan = Plan(handle, nslots, fresh, scratch, result_spec, b.constants, rec, take, rewind, guards, b.device)
     plan.scratch_refs = b.scratch_refs
     # the recursive spec_of closure keeps this frame (and through it every traced tensor) in a reference cycle: let go explicitly
     b.temp_ranges, b.slots, b.slot_of = [], [], {}

@@ -528,6 +528,7 @@ def test_a_planned_perlin_call_is_one_launch(api, shape):
     assert plan is not None and hl.load().sonar_plan_length(plan.handle) == 1
     hook = plan.hooks[0]
     assert isinstance(hook, hl._PerlinAheadHook) and hook.hits >= 6 and hook.misses >= 3  # first run, the reseed, the foreign draw
+    assert plan.scratch == []  # the lattice and statistics operands the rewrite dropped get no per-stream scratch
     # the entry point itself: every combination of what a call may find, against the three launches it replaces
     lib = hl.load()
     b_, c, h, w = (shape[0], math.prod(shape[1:-2]), shape[-2], shape[-1])

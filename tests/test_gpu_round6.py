@@ -99,6 +99,7 @@ def test_a_planned_normalised_fill_runs_its_statistics_a_call_ahead(api, name, s
     assert plan is not None, getattr(planned, "reason", None)
     hooks = [h for h in plan.hooks if isinstance(h, hl._FillAheadHook)]
     assert len(hooks) == 1 and hooks[0].hits >= 6 and hooks[0].misses >= 3  # first run, the reseed, the foreign draw
+    assert plan.scratch == []  # the statistics operand the rewrite dropped gets no per-stream scratch
     # the same sampler with the look-ahead switched off plans the two-launch form: same bits again
     old = hl.FILL_AHEAD
     hl.FILL_AHEAD = False
@@ -255,6 +256,7 @@ def test_a_planned_normalised_pyramid_call_is_one_launch(api, shape):
     assert hl.load().sonar_plan_length(plan.handle) == 1
     hooks = [h for h in plan.hooks if isinstance(h, hl._FillAheadHook)]
     assert len(hooks) == 1 and hooks[0].hits >= 5 and hooks[0].misses >= 2, (hooks[0].hits, hooks[0].misses)
+    assert plan.scratch == []  # the statistics operand the rewrite dropped gets no per-stream scratch
     old = hl.PYRAMID_AHEAD
     hl.PYRAMID_AHEAD = False
     try:

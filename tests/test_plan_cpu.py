@@ -2,7 +2,9 @@
 device-mode pyramid draw against the Python sequence it replaces, and the plan object's argument validation.  No kernel is launched."""
 import ctypes as C
 import importlib
+import os
 import random
+import re
 
 import pytest
 
@@ -74,6 +76,20 @@ def test_every_launch_only_entry_point_the_plans_name_exists(pkg):
         restype, argtypes = hl.SIGNATURES[n]
         assert restype is C.c_int and argtypes[-1] is C.c_void_p, n
         assert lib.sonar_plan_fn_nargs(lib.sonar_plan_fn_id(n.encode())) == len(argtypes), n
+
+
+def test_the_rewrites_parameter_names_are_the_headers(pkg):
+    """The plan rewrites address arguments by name (``hip_lib._PARAMS``): each name tuple is its entry point's parameter list as
+    include/sonar_hip.h declares it, and as long as the ctypes signature -- a parameter added to one of them cannot shift a rewrite."""
+    hl = pkg.hip_lib
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sonar_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert len(hl._PARAMS) == 9
+    for name, params in hl._PARAMS.items():
+        decl = re.search(rf"\b{name}\s*\(([^)]*)\)", text)
+        assert decl is not None, name
+        assert params == tuple(re.search(r"(\w+)\s*$", p).group(1) for p in decl.group(1).split(",")), name
+        assert len(params) == len(hl.SIGNATURES[name][1]), name
 
 
 def test_blob_words(pkg):
