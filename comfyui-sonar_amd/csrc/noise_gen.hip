@@ -43,17 +43,20 @@ __device__ __forceinline__ void for_each_group(int64_t n, uint64_t seed, uint64_
     }
 }
 
+// (sum, sumsq) of one whole group of four values, as the 16-byte store paths reduce them
+__device__ __forceinline__ void group_stats(const float (&v)[4], double& s, double& q) {
+    const float ps = (v[0] + v[1]) + (v[2] + v[3]);
+    const float pq = __builtin_fmaf(v[0], v[0], __builtin_fmaf(v[1], v[1], __builtin_fmaf(v[2], v[2], v[3] * v[3])));
+    s += (double)ps;
+    q += (double)pq;
+}
+
 // store 4 values at local index e with range / alignment handling; returns how many were in range
 template <bool VEC>
 __device__ __forceinline__ void store_group(float* out, int64_t n, int64_t e, const float (&v)[4], double& s, double& q, bool stats) {
     if (VEC && e >= 0 && e + 4 <= n) {
         *reinterpret_cast<float4*>(out + e) = make_float4(v[0], v[1], v[2], v[3]);
-        if (stats) {
-            const float ps = (v[0] + v[1]) + (v[2] + v[3]);
-            const float pq = __builtin_fmaf(v[0], v[0], __builtin_fmaf(v[1], v[1], __builtin_fmaf(v[2], v[2], v[3] * v[3])));
-            s += (double)ps;
-            q += (double)pq;
-        }
+        if (stats) group_stats(v, s, q);
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -2060,11 +2063,27 @@ struct BrownianBase {
 };
 // PRE: 0 none, 1 Gaussian draw, 2 Perlin (summed lattice, tile-aligned latents).  With a prefix a wave walks the kBrownPerTile
 // consecutive Brownian tiles of one generator tile, carrying the prefix's generator state across them.
+// VEC = false: some buffer is only 4-byte aligned (a view at an odd storage offset) -- four 4-byte accesses where the kernel would
+// make one 16-byte one, the same arithmetic and statistics order: the value family is a function of the shape, never of an address.
 constexpr int kBrownPerTile = kTileElems / (4 * 256);
-template <int PRE, int BLOCK>
+template <bool VEC>
+__device__ __forceinline__ float4 brown_ld4(const float* p) {
+    if constexpr (VEC) return *reinterpret_cast<const float4*>(p);
+    else return make_float4(p[0], p[1], p[2], p[3]);
+}
+template <bool VEC>
+__device__ __forceinline__ void brown_st4(float* p, const float4& v) {
+    if constexpr (VEC) {
+        *reinterpret_cast<float4*>(p) = v;
+    } else {
+        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+    }
+}
+template <int PRE, int BLOCK, bool VEC = true>
 __global__ void __launch_bounds__(BLOCK) brownian_burst_kernel(float* out, int64_t n, int64_t elem_offset, BrownianBurstTerms terms,
                                                                 uint64_t seed, const float* prev, float* w_out, float scale,
                                                                 BrownianBase base, Accum fold, double* partials, Prefix pre) {
+    static_assert(VEC || PRE == 0, "a hosted prefix reads the running sum 16 bytes at a time");
     kernarg_touch_for(out, n, elem_offset, terms, seed, prev, w_out, scale, base, fold, partials, pre);
     __shared__ double red[2 * BLOCK / 64];
     double s = 0.0, q = 0.0;
@@ -2093,11 +2112,11 @@ __global__ void __launch_bounds__(BLOCK) brownian_burst_kernel(float* out, int64
             for (int it = 0; it < kBrownIters; ++it) {
                 float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (base.a) {
-                    const float4 p = *reinterpret_cast<const float4*>(base.a + o + it * 256);
+                    const float4 p = brown_ld4<VEC>(base.a + o + it * 256);
                     v = make_float4(base.fa * p.x, base.fa * p.y, base.fa * p.z, base.fa * p.w);
                 }
                 if (base.b) {
-                    const float4 p = *reinterpret_cast<const float4*>(base.b + o + it * 256);
+                    const float4 p = brown_ld4<VEC>(base.b + o + it * 256);
                     v = make_float4(__builtin_fmaf(base.fb, p.x, v.x), __builtin_fmaf(base.fb, p.y, v.y), __builtin_fmaf(base.fb, p.z, v.z),
                                     __builtin_fmaf(base.fb, p.w, v.w));
                 }
@@ -2116,10 +2135,10 @@ __global__ void __launch_bounds__(BLOCK) brownian_burst_kernel(float* out, int64
 #pragma unroll
             for (int it = 0; it < kBrownIters; ++it) {
                 float4 a = make_float4(acc[it][0], acc[it][1], acc[it][2], acc[it][3]);
-                if (w_out) *reinterpret_cast<float4*>(w_out + o + it * 256) = a;
+                if (w_out) brown_st4<VEC>(w_out + o + it * 256, a);
                 if (out) {
                     if (prev) {
-                        const float4 p = *reinterpret_cast<const float4*>(prev + o + it * 256);
+                        const float4 p = brown_ld4<VEC>(prev + o + it * 256);
                         a = make_float4(a.x - p.x, a.y - p.y, a.z - p.z, a.w - p.w);
                     }
                     float v[4] = {a.x * scale, a.y * scale, a.z * scale, a.w * scale};
@@ -2132,9 +2151,14 @@ __global__ void __launch_bounds__(BLOCK) brownian_burst_kernel(float* out, int64
                         prefix_draw<PRE>(prng, dv, tv, x);
                         prefix_fold(pre, pfold, fold, o + it * 256, x, v);
                     } else {
-                        accumulate_group<true>(fold, n, o + it * 256, v);
+                        accumulate_group<VEC>(fold, n, o + it * 256, v);  // (whole tiles: every element in range)
                     }
-                    store_group<true>(out, n, o + it * 256, v, s, q, partials != nullptr);
+                    if constexpr (VEC) {
+                        store_group<true>(out, n, o + it * 256, v, s, q, partials != nullptr);
+                    } else {
+                        brown_st4<false>(out + o + it * 256, make_float4(v[0], v[1], v[2], v[3]));
+                        if (partials) group_stats(v, s, q);
+                    }
                 }
             }
         }
@@ -2316,9 +2340,12 @@ static int brownian_launch(float* out, float* w_out, const float* prev, float sc
         bt.hc[k] = (uint32_t)(h >> 32);
     }
     auto al = [](const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-    // the variant is a function of the latent size and the seed kind only, so every shard of a batch picks the same one
+    // the variant is a function of the latent size and the seed kind only, so every shard of a batch picks the same one; buffer
+    // addresses choose only how the burst kernel accesses memory (a 4-byte-aligned buffer once switched the call to the Philox family:
+    // other values for the same seed, node and element)
     const bool burst = !latent_seeds && latent_elems > 0 && latent_elems % kTileElems == 0 && n % latent_elems == 0 &&
-                       elem_offset % latent_elems == 0 && al(out) && al(w_out) && al(prev) && al(base.a) && al(base.b) && al(acc.y);
+                       elem_offset % latent_elems == 0;
+    const bool vec = al(out) && al(w_out) && al(prev) && al(base.a) && al(base.b) && al(acc.y);
     SONAR_REQUIRE(!partials || out, SONAR_ERR_ARG, "%s: statistics need an output tensor", what);
     // statistics: one (sum, sumsq) pair per block, at most kNPart blocks
     const int cap = partials ? kNPart : kMaxGrid;
@@ -2327,23 +2354,25 @@ static int brownian_launch(float* out, float* w_out, const float* prev, float sc
         // the previous chain item rides along only in the tile kernel, on the same running sum, with whole generator tiles per latent
         const int prc = make_prefix(pre, px, what);
         if (prc != SONAR_OK) return prc;
-        SONAR_REQUIRE(burst && acc.y && out == acc.y && (pre->kind != SONAR_PREFIX_PERLIN || pre->chw == latent_elems), SONAR_ERR_UNSUPPORTED,
+        SONAR_REQUIRE(burst && vec && acc.y && out == acc.y && (pre->kind != SONAR_PREFIX_PERLIN || pre->chw == latent_elems), SONAR_ERR_UNSUPPORTED,
                       "%s: this shape cannot host a fold prefix (apply it with its own entry point)", what);
     }
-#define SONAR_BBL(P, BL) \
-    hipLaunchKernelGGL((brownian_burst_kernel<P, BL>), dim3(std::min(cap, grid_for(n / (kBrownTile * (P ? kBrownPerTile : 1)), BL / 64))), dim3(BL), 0, \
+#define SONAR_BBL(P, BL, V) \
+    hipLaunchKernelGGL((brownian_burst_kernel<P, BL, V>), dim3(std::min(cap, grid_for(n / (kBrownTile * (P ? kBrownPerTile : 1)), BL / 64))), dim3(BL), 0, \
                        (hipStream_t)stream, out, n, elem_offset, bt, seed, prev, w_out, scale, base, acc, partials, px)
-#define SONAR_BB(P) \
+#define SONAR_BB(P, V) \
     do { \
-        if (nnodes >= kBrownLongTerms) SONAR_BBL(P, kBrownBlock); \
-        else SONAR_BBL(P, kBlock); \
+        if (nnodes >= kBrownLongTerms) SONAR_BBL(P, kBrownBlock, V); \
+        else SONAR_BBL(P, kBlock, V); \
     } while (0)
     if (burst && pre && pre->kind == SONAR_PREFIX_NORMAL)
-        SONAR_BB(1);
+        SONAR_BB(1, true);
     else if (burst && pre)
-        SONAR_BB(2);
+        SONAR_BB(2, true);
+    else if (burst && vec)
+        SONAR_BB(0, true);
     else if (burst)
-        SONAR_BB(0);
+        SONAR_BB(0, false);
 #undef SONAR_BBL
 #undef SONAR_BB
     else

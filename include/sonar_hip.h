@@ -56,7 +56,11 @@ const char* sonar_last_error(void);
  *   3: round 3 (xoshiro128 bursts seeded by Philox4x32-10 at three depths)
  *   5: round 5 (MWC64X bursts; power-law spectra: filter weight under the radius' square root, 23 radius / 16 angle bits)
  *   6: round 6 (Brownian noise only: node bursts seeded by hashing a per-sub-tile Philox state with the node id, the power-law draw's
- *      conversions; every other generator's values are version 5's) */
+ *      conversions; every other generator's values are version 5's).  Version 6 has TWO Brownian families: the node bursts for one
+ *      seed and latents of a multiple of 4096 elements with the call on whole latents, one Philox4x32-10 block per 4 values (counter =
+ *      (element / 4, node id), key = seed) for per-latent seeds and every other shape -- a function of the shape and the seed kind,
+ *      never of buffer addresses (sonar_brownian_f32).
+ * oracle/device_streams.py states every generate-mode stream in numpy; a change of values bumps this number and that file together. */
 int sonar_noise_stream_version(void);
 
 /* ---------------------------------------------------------------- normalisation (row N) */
@@ -259,9 +263,12 @@ int sonar_philox_noise_ahead_f32(int uniform, float* out, int64_t n, uint64_t se
  * z a counter-based N(0,1) keyed by (seed, node id (48 bits), global element index elem_offset + e).  node_ids / coefs are
  * HOST arrays (<= 96 entries): the expansion of the queried increment / point over the node normals, kept by the host in fp64
  * (each queried time is a Brownian bridge between the nearest times known before it).  latent_elems =
- * elements per latent (0 if unknown): when it is a multiple of 4096 and there is one seed, z(node, .) is the tile-keyed burst
- * stream of the Gaussian fill with stream id = node (one Philox seeding per 64 values); otherwise one Philox4x32-10 call per
- * 4 values.  latent_seeds (device, nullable): one seed per latent (the sampler's batched-seed mode), replacing `seed`. */
+ * elements per latent (0 if unknown): when it is a multiple of 4096, there is one seed and the call covers whole latents, z(node, .)
+ * is a node burst: per 1024-element sub-tile and lane ONE base state rng_stream(seed, 0xB0B000000001, sub-tile, lane), per node a
+ * multiply-with-carry burst seeded with fmix32(base.x ^ hx), fmix32(base.c ^ hc), (hx, hc) = splitmix64(node id), 12 words per lane
+ * (23 radius bits, 16 angle bits per value); otherwise one Philox4x32-10 block per 4 values (counter (element / 4, node id), key seed).
+ * The family never depends on buffer alignment (4-byte-aligned buffers take the same values).  latent_seeds (device, nullable): one
+ * seed per latent (the sampler's batched-seed mode), replacing `seed` (always the Philox family). */
 int sonar_brownian_f32(float* out, int64_t n, int64_t elem_offset, const uint64_t* node_ids, const float* coefs, int nnodes,
                        uint64_t seed, const uint64_t* latent_seeds, int64_t latent_elems, void* stream);
 /* One path point instead of an increment: W = sum_k coefs[k] z(node_ids[k], e) with the coefficients of W(t) itself;

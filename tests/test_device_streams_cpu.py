@@ -1,0 +1,200 @@
+"""CPU: the numpy statement of the generate-mode streams (oracle/device_streams.py) against published known-answer vectors and plain
+Python integers, the draw orders of the half-spectrum against the half-spectrum itself, and the host's Brownian expansion against an
+independent evaluation of the virtual Brownian tree.  The GPU side (tests/test_gpu_generate_oracle.py) compares the kernels with it."""
+import math
+import random
+
+import numpy as np
+import pytest
+
+from oracle import device_streams as ds
+
+
+def _hex(words):
+    return " ".join("%08x" % int(w) for w in words)
+
+
+@pytest.mark.parametrize("ctr, key, want", [
+    ((0, 0, 0, 0), (0, 0), "6627e8d5 e169c58d bc57ac4c 9b00dbd8"),
+    ((0xFFFFFFFF,) * 4, (0xFFFFFFFF,) * 2, "408f276d 41c83b0e a20bc7c6 6d5451fd"),
+    ((0x243F6A88, 0x85A308D3, 0x13198A2E, 0x03707344), (0xA4093822, 0x299F31D0), "d16cfe09 94fdcceb 5001e420 24126ea1"),
+])
+def test_philox4x32_10_known_answers(ctr, key, want):
+    """Random123's kat_vectors for philox4x32-10, scalar and broadcast over an array."""
+    assert _hex(ds.philox4x32_10(*ctr, *key)) == want
+    arr = ds.philox4x32_10(*(np.full(3, c, dtype=np.uint64) for c in ctr), *key)
+    assert all(_hex(w[i] for w in arr) == want for i in range(3))
+
+
+def test_philox_extra_rounds_continue_the_key_schedule():
+    """The spectrum's edge stream: 12 rounds = 10 rounds, then 2 more with the key bumped 10 times."""
+    c, k = (1, 2, 3, 4), (5, 6)
+    w10 = ds.philox4x32(*c, *k, rounds=10)
+    k10 = ((5 + 10 * 0x9E3779B9) & 0xFFFFFFFF, (6 + 10 * 0xBB67AE85) & 0xFFFFFFFF)
+    two_more = [int(v) for v in ds.philox4x32(*w10, *k10, rounds=2)]
+    assert [int(v) for v in ds.philox4x32(*c, *k, rounds=12)] == two_more
+
+
+def test_hash_known_answers():
+    assert ds.splitmix64(0) == 0xE220A8397B1DCDAF
+    assert int(ds.fmix32(1)) == 0x514E28B7
+    assert int(ds.fmix32(0)) == 0
+
+
+def test_mwc_steps_against_python_integers():
+    rnd = random.Random(3)
+    for _ in range(50):
+        a, b = rnd.getrandbits(32), rnd.getrandbits(32)
+        g = ds.Mwc.seeded(a, b)
+        x, c = a, (b >> 1) | 1
+        assert 1 <= c < 2**31
+        for _ in range(20):
+            assert int(g.next()) == x ^ c
+            t = ds.MWC_A * x + c
+            x, c = t & 0xFFFFFFFF, t >> 32
+
+
+def test_rng_stream_key_word_and_truncated_stream_bits():
+    """The fourth counter word is ((stream >> 32) << 16) ^ lane truncated to 32 bits: bits 48..63 of a stream id do not reach it, bits 32..47
+    do, and the lane is folded into the same word."""
+    s = 0x0000_1234_89AB_CDEF
+
+    def first_words(stream, lane):
+        return [int(v) for v in ds.rng_stream(7, stream, 5, lane).words(4)]
+
+    assert first_words(s, 3) == first_words(s | (0xBEEF << 48), 3)
+    assert first_words(s, 3) != first_words(s ^ (1 << 32), 3)
+    assert first_words(s, 3) != first_words(s, 2)
+    w = ds.philox4x32_10(5, 0, s & 0xFFFFFFFF, (((s >> 32) << 16) & 0xFFFFFFFF) ^ 3, 7, 0)
+    g = ds.Mwc.seeded(w[0] ^ w[2], w[1] ^ w[3])
+    assert first_words(s, 3) == [int(v) for v in g.words(4)]
+
+
+def test_tile_walk_maps_elements_to_words():
+    """Element e is word 4 * step + slot of lane (e % 256) // 4's burst in tile e // 4096 -- stream_words states the walk through the
+    bursts themselves; the two must agree for any window."""
+    e = np.array([0, 1, 3, 4, 255, 256, 4095, 4096, 4097, 7 * 4096 + 2, 3 * 4096 + 4])
+    tile, lane, step, slot = ds.tile_position(e)
+    assert list(tile[-4:]) == [1, 1, 7, 3] and list(lane[:6]) == [0, 0, 0, 1, 63, 0] and step[6] == 15 and list(slot[:4]) == [0, 1, 3, 0]
+    for seed, stream in ((0, 0), (2**32 + 5, 2**47 + 1), (2**64 - 1, 2**32 + 3)):
+        words = ds.stream_words(seed, stream, 8 * 4096)
+        for i in range(len(e)):
+            g = ds.rng_stream(seed, stream, int(tile[i]), int(lane[i]))
+            assert int(words[e[i]]) == int(g.words(64)[4 * step[i] + slot[i]])
+        # a window at an offset is the same stream
+        assert np.array_equal(ds.stream_words(seed, stream, 5000, 4093), words[4093:4093 + 5000])
+
+
+def test_conversions_are_exact_in_fp32():
+    w = np.array([0, 1, 0xFF, 0x100, 0x7FFFFFFF, 0xFFFFFF00, 0xFFFFFFFF], dtype=np.uint64)
+    for f in (ds.u01, ds.u01_open, ds.unit_mantissa_radius):
+        v = f(w)
+        assert np.array_equal(v.astype(np.float32).astype(np.float64), v)
+    assert ds.u01(w).min() == 0.0 and ds.u01(w).max() < 1.0
+    assert ds.u01_open(w).min() == 2.0**-25 and ds.u01_open(0x7FFFFFFF) == 0.5 - 2.0**-25
+    assert ds.u01_open(0xFFFFFFFF) == 1.0 and ds.u01_open(0xFFFFFE00) == 1.0 - 2.0**-23  # fp32 ties to even
+    u = ds.unit_mantissa_radius(w)
+    assert u.max() == 1.0 and u.min() > 0.0 and ds.unit_mantissa_radius(0xFFFFFFFF) == 2.0**-23
+    # angles: 16 bits each as fractions of a revolution -- the float the kernel builds is 128 + bits 0..22 / 2^16 (low half) or
+    # 128 + bits 16..31 / 2^16 (high half), equal to these modulo whole revolutions
+    t = np.array([0x12345678, 0xFFFF0000, 0x0000FFFF, 0x007FFFFF], dtype=np.uint64)
+    lo_float = 128.0 + (t & np.uint64(0x7FFFFF)).astype(np.float64) * 2.0**-16
+    hi_float = 128.0 + (t >> np.uint64(16)).astype(np.float64) * 2.0**-16
+    assert np.array_equal(np.mod(lo_float, 1.0), ds.angle_lo(t)) and np.array_equal(np.mod(hi_float, 1.0), ds.angle_hi(t))
+    assert ds.angle_lo(0x12345678) == 0x5678 / 65536 and ds.angle_hi(0x12345678) == 0x1234 / 65536
+
+
+def test_normal_and_uniform_fills_are_windows_of_one_stream():
+    seed, stream = 2**32 + 5, 2**32 + 3
+    whole = ds.normal_fill(seed, stream, 4 * 4096 + 7)
+    for off, n in ((0, 1), (1, 3), (4093, 4097), (7, 3 * 4096)):
+        assert np.array_equal(ds.normal_fill(seed, stream, n, off), whole[off:off + n])
+    z = ds.normal_fill(0, 0, 1 << 17)
+    assert abs(z.mean()) < 0.02 and abs(z.std() - 1.0) < 0.02
+    u = ds.uniform_fill(0, 0, 1 << 17)
+    assert u.dtype == np.float32 and 0.0 <= u.min() and u.max() < 1.0 and abs(u.mean() - 0.5) < 0.01
+    # Box-Muller pairs: slots 0 / 1 share a radius, as do 2 / 3
+    g, w = whole[:4 * 4096].reshape(-1, 4), ds.stream_words(seed, stream, 4 * 4096).reshape(-1, 4)
+    assert np.allclose(np.hypot(g[:, 0], g[:, 1]), np.sqrt(-2 * np.log(ds.u01_open(w[:, 0]))), rtol=1e-12)
+    assert np.allclose(np.hypot(g[:, 2], g[:, 3]), np.sqrt(-2 * np.log(ds.u01_open(w[:, 2]))), rtol=1e-12)
+
+
+def test_brownian_families_and_selector():
+    assert ds.brownian_family(4 * 4096, 0, 4096) == "burst"
+    assert ds.brownian_family(4 * 4096, 4096, 4096) == "burst"        # a shard on a latent boundary
+    assert ds.brownian_family(4 * 4096, 2048, 4096) == "philox"       # not on a latent boundary
+    assert ds.brownian_family(4 * 900, 0, 900) == "philox"            # latents not whole tiles
+    assert ds.brownian_family(4 * 4096, 0, 4096, latent_seeds=[1, 2, 3, 4]) == "philox"
+    # both are unit normals per node, independent across nodes
+    for z in (ds.brownian_burst_z(11, [0, 1, 2**40 + 3], 4 * 4096), ds.brownian_philox_z(11, [0, 1, 2**40 + 3], 4 * 4096)):
+        assert np.all(np.abs(z.mean(axis=1)) < 0.04) and np.all(np.abs(z.std(axis=1) - 1.0) < 0.04)
+        assert abs(np.corrcoef(z[0], z[1])[0, 1]) < 0.04
+    # the burst family's sub-tiles: a window is the same stream
+    z = ds.brownian_burst_z(11, [5], 3 * 1024)
+    assert np.array_equal(ds.brownian_burst_z(11, [5], 1024, 1024), z[:, 1024:2048])
+    # the Philox family is philox_normal4 of counter (e // 4, node); per-latent seeds restart the counter in every latent
+    zp = ds.brownian_philox_z(11, [9], 12, 2)
+    assert np.array_equal(zp[0], ds.philox_normal4(11, 9, np.arange(4)).reshape(-1)[2:14])
+    zl = ds.brownian_philox_z(0, [9], 16, 8, latent_seeds=[21, 22], latent_elems=8)
+    assert np.array_equal(zl[0, 8:], ds.philox_normal4(22, 9, np.arange(2)).reshape(-1))
+
+
+# ------------------------------------------------------------------------------------------------ half-spectrum draw orders
+@pytest.mark.parametrize("shape", list(ds.FIXED_PLANES) + [(104, 152), (96, 168), (256, 256)])
+def test_every_half_spectrum_element_is_drawn_once(shape):
+    H, W = shape
+    kind = 1 if shape in ds.FIXED_PLANES else 4 if shape == (256, 256) else 2
+    counts, discarded = ds.spectrum_draw_order(H, W, kind)
+    assert counts.shape == (H, W // 2 + 1) and counts.min() == 1 and counts.max() == 1
+    assert discarded == (H // 2 if kind in (1, 2) else 0)  # only the kx = M pair slot of each row pair
+    if kind == 1:
+        assert H <= ds.plane_threads(H, W)  # edge rows are slots of the workgroup
+
+
+def test_spectrum_draws_are_unit_complex_normals_keyed_by_group():
+    z = ds.spectrum_draws(3, 2**32 + 3, 8, 64, 64, 0, 4, 1)
+    assert np.all(z != 0) and abs(np.mean(np.abs(z) ** 2) - 1.0) < 0.02
+    # a plane's values depend on its global index only: a window of planes at an offset matches
+    assert np.array_equal(ds.spectrum_draws(3, 2**32 + 3, 3, 64, 64, 5, 4, 1), z[5:8])
+    assert np.array_equal(ds.spectrum_draws(3, 7, 2, 104, 152, 1, 1, 2), ds.spectrum_draws(3, 7, 3, 104, 152, 0, 1, 2)[1:])
+
+
+# ------------------------------------------------------------------------------------------------ host expansion vs the oracle tree
+def _grid_queries(rnd, lo, hi, D, k):
+    cells = 1 << D
+    ts = [lo + rnd.randrange(1, cells) * (hi - lo) / cells for _ in range(k)]
+    ts += [rnd.uniform(lo, hi) for _ in range(k)]
+    ts += [lo, hi, hi + 0.3 * (hi - lo) / cells, lo - 0.3 * (hi - lo) / cells]  # ends, and times that snap onto them
+    ts += ts[:5]                                                                   # repeated queries
+    rnd.shuffle(ts)
+    return ts
+
+
+@pytest.mark.parametrize("D", [24, 6])
+def test_brownian_path_equals_the_oracle_tree(pkg, D):
+    import importlib
+
+    ng = importlib.import_module("comfyui_sonar_amd.py.noise_generation")
+    lo, hi = 0.0292, 14.6146
+    rnd = random.Random(D)
+    bp = ng.BrownianPath(lo, hi, D)
+    assert bp.tree_depth == D
+
+    def close(got, want):
+        keys = set(got) | set(want)
+        assert all(abs(got.get(k, 0.0) - want.get(k, 0.0)) <= 1e-12 for k in keys), (got, want)
+
+    ts = _grid_queries(rnd, lo, hi, D, 40)
+    for t in ts:
+        close(bp.coefficients(t), ds.tree_point(lo, hi, D, bp.grid_index(bp.resolve(t))))
+    for t0, t1 in zip(ts[:-1], ts[1:]):
+        g0, g1 = bp.grid_index(bp.resolve(t0)), bp.grid_index(bp.resolve(t1))
+        if g0 == g1:
+            continue
+        ids, co = bp.increment(t0, t1)
+        want = {k: v for k, v in ds.tree_increment(lo, hi, D, g0, g1).items() if abs(v) > 1e-12}
+        close(dict(zip(ids, co)), want)
+    # the oracle tree is a Brownian motion: Var W(t) = t - t_lo
+    for g in (1, 5, (1 << D) - 1):
+        c = ds.tree_point(lo, hi, D, g)
+        assert math.isclose(sum(v * v for v in c.values()), ds.tree_grid_time(lo, hi, D, g) - lo, rel_tol=1e-12)

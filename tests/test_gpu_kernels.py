@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from oracle import sonar_oracle as orc
+from oracle.device_streams import philox4x32_10 as _philox4x32_10
 
 pytestmark = pytest.mark.gpu
 
@@ -699,21 +700,6 @@ def test_c_abi_error_codes_and_messages(hl):
 
 
 # ------------------------------------------------------------------------------------------------ Perlin lattice drawn in-kernel
-def _philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Reference Philox4x32-10 on numpy uint64 lanes (Salmon et al.); returns the four 32-bit words."""
-    import numpy as np
-
-    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), 0x9E3779B9, 0xBB67AE85
-    mask = np.uint64(0xFFFFFFFF)
-    c0, c1, c2, c3 = (np.asarray(v, dtype=np.uint64) & mask for v in (c0, c1, c2, c3))
-    for r in range(10):
-        p0, p1 = M0 * c0, M1 * c2
-        hi0, lo0, hi1, lo1 = p0 >> np.uint64(32), p0 & mask, p1 >> np.uint64(32), p1 & mask
-        kk0, kk1 = np.uint64((k0 + r * W0) & 0xFFFFFFFF), np.uint64((k1 + r * W1) & 0xFFFFFFFF)
-        c0, c1, c2, c3 = (hi1 ^ c1 ^ kk0) & mask, lo1, (hi0 ^ c3 ^ kk1) & mask, lo0
-    return c0, c1, c2, c3
-
-
 @pytest.mark.parametrize("blend_mode", ["lerp", "inject"])
 def test_perlin_lattice_kernel_against_a_host_replay_of_its_draws(hl, blend_mode):
     """sonar_perlin_lattice_f32 draws angle(it, c, gy, gx) = 2 pi u, u = word[it % 4] >> 8 * 2^-24 of
