@@ -137,6 +137,11 @@ SIGNATURES = {
     "sonar_studentt_f32": (_I, [_P, _P, _F, _F, _F, _I64, _P]),
     "sonar_abs_quantile_rows_f32": (_I, [_P, _I64, _I64, _I64, _F, _P, _P]),
     "sonar_clamp_signpow_rows_f32": (_I, [_P, _I64, _I64, _P, _F, _F, _P]),
+    "sonar_quantile_rows_ws_bytes": (_I64, [_I64, _I64, _I]),
+    "sonar_quantile_rows_f32": (_I, [_P, _I64, _I64, _I64, _F, _F, _F, _I, _I, _F, _P, _P, _P, _P]),
+    "sonar_quantile_replace_ws_elems": (_I64, [_I64]),
+    "sonar_quantile_replace_compact_f32": (_I, [_P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
+    "sonar_quantile_replace_apply_f32": (_I, [_P, _P, _I64, _I64, _I64, _I, _P, _P, _I, _I, _I, _F, _P, _P]),
     "sonar_mul_table_f32": (_I, [_P, _P, _I64, _I64, _I64, _I, _P]),
     "sonar_laplace_add_f32": (_I, [_P, _P, _F, _F, _F, _I64, _P]),
     "sonar_power_plane_kind": (_I, [_I64, _I64]),
@@ -485,6 +490,52 @@ def clamp_signpow_rows_(x: torch.Tensor, rows: int, inner: int, limit: torch.Ten
     _check(load().sonar_clamp_signpow_rows_f32(_dev(x, "x"), rows, inner, _dev(limit, "limit"), float(mul), float(p), _stream()),
            "sonar_clamp_signpow_rows_f32")
     return x
+
+
+def quantile_rank(q: float, inner: int):
+    """(lo, frac) of torch.quantile's linear interpolation: rank = q * (inner - 1) formed in fp32, lo = floor(rank)."""
+    rank = torch.tensor(q, dtype=torch.float32) * (inner - 1)
+    lo = int(torch.floor(rank).item())
+    return min(lo, inner - 1), float((rank - lo).item())
+
+
+# strategy codes of sonar_quantile_rows_f32 (include/sonar_hip.h SONAR_Q_*)
+Q_CLAMP, Q_TANH, Q_TANH_OUTLIERS, Q_SIGMOID, Q_SIGMOID_KEEPSIGN, Q_SIGMOID_OUTLIERS, Q_ATAN, Q_TENTH, Q_HALF, Q_ZERO, Q_REVERSE_ZERO = range(11)
+Q_SCALE_DOWN, Q_MEAN, Q_MEDIAN, Q_MODE_1DEC, Q_MODE_2DEC, Q_WAVE = range(11, 17)
+Q_WAVE_COS, Q_WAVE_WHOLEPI, Q_WAVE_WRONG, Q_WAVE_KEEPSIGN = 0x100, 0x200, 0x400, 0x800
+
+
+def quantile_rows(x: torch.Tensor, rows: int, inner: int, q: float, nq_fac: float, eps: float, op: int, centered: bool, pow_fac: float,
+                  out: Optional[torch.Tensor]) -> torch.Tensor:
+    """sonar_quantile_rows_f32: the filter over rows of ``inner`` contiguous values of ``x`` into ``out`` (None: statistics only); returns
+    the [rows, 3] row statistics (nq, max|x|, second statistic)."""
+    lo, frac = quantile_rank(q, inner)
+    stats = torch.empty((rows, 3), dtype=torch.float32, device=x.device)
+    nbytes = int(load().sonar_quantile_rows_ws_bytes(rows, inner, int(op)))
+    if nbytes < 0:
+        raise SonarHipError(f"sonar_quantile_rows_ws_bytes: bad shape ({rows}, {inner})")
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _check(load().sonar_quantile_rows_f32(_dev(x, "x"), rows, inner, lo, frac, float(nq_fac), float(eps), int(op), int(bool(centered)),
+                                          float(pow_fac), _opt(out, "out"), _dev(stats, "stats"), _dev(ws, "ws", torch.uint8) if nbytes else None,
+                                          _stream()),
+           "sonar_quantile_rows_f32")
+    return stats
+
+
+def quantile_replace(x: torch.Tensor, stats: torch.Tensor, length: int, stride: int, centered: bool, count: int, flip: bool, sign_mode: int,
+                     pow_fac: float, out: torch.Tensor) -> int:
+    """The replace* strategies over all of ``x`` (memory order); returns the number of candidates, read back to the host (0: nothing written)."""
+    n = x.numel()
+    cand = torch.empty(n, dtype=torch.float32, device=x.device)
+    counts = torch.empty(int(load().sonar_quantile_replace_ws_elems(n)), dtype=torch.int64, device=x.device)
+    _check(load().sonar_quantile_replace_compact_f32(_dev(x, "x"), _dev(stats, "stats"), n, length, stride, int(bool(centered)),
+                                                     _dev(cand, "cand"), _dev(counts, "counts", torch.int64), _stream()),
+           "sonar_quantile_replace_compact_f32")
+    _check(load().sonar_quantile_replace_apply_f32(_dev(x, "x"), _dev(stats, "stats"), n, length, stride, int(bool(centered)), _dev(cand, "cand"),
+                                                   _dev(counts, "counts", torch.int64), int(count), int(bool(flip)), int(sign_mode),
+                                                   float(pow_fac), _dev(out, "out"), _stream()),
+           "sonar_quantile_replace_apply_f32")
+    return int(counts[-1].item())
 
 
 def mul_table_(x: torch.Tensor, table: torch.Tensor, inner: int, follow_sign: bool = False) -> torch.Tensor:

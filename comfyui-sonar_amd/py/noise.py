@@ -708,6 +708,28 @@ class LatentOperationFilteredNoise(CustomNoiseItemBase):
         return noise_sampler
 
 
+class QuantileFilteredNoise(CustomNoiseItemBase):
+    """py/noise.py:1777-1819: a chain's noise through utils.quantile_normalize (HIP radix select + strategy kernels), then scaled."""
+
+    def clone_key(self, k):
+        if k == "noise":
+            return self.noise.clone()
+        return super().clone_key(k)
+
+    def make_noise_sampler(self, x, sigma_min, sigma_max, *args, normalized=True, **kwargs):
+        factor = self.factor
+        normalize = self.get_normalize("normalize", normalized)
+        ns = self.noise.make_noise_sampler(x, *args, sigma_min=sigma_min, sigma_max=sigma_max, normalized=self.normalize_noise, **kwargs)
+        noise_filter = partial(utils.quantile_normalize, quantile=self.quantile, dim=self.norm_dim, flatten=self.norm_flatten,
+                               nq_fac=self.norm_fac, pow_fac=self.norm_pow, strategy=self.strategy)
+
+        def noise_sampler(sigma, sigma_next):
+            noise = noise_filter(ns(sigma, sigma_next))
+            return scale_noise(noise.contiguous(), factor, normalized=normalize)
+
+        return noise_sampler
+
+
 class RippleFilteredNoise(CustomNoiseItemBase):
     """py/noise.py:1134-1202: the chain's noise times a sin / cos gain profile along one dimension (or the flattened trailing ones),
     rolled a little further every call."""

@@ -244,3 +244,155 @@ def tensor_item(val, *, collapse_function=torch.max) -> float:
     if isinstance(val, Tensor):
         return float(collapse_function(val).detach().cpu().item())
     return float(val)
+
+
+# --------------------------------------------------------------------------------------------------
+# quantile filtering (py/utils.py:123-449)
+class QuantileStrategy:
+    """How one entry of ``quantile_handlers`` runs on the device: a row-kernel strategy code (include/sonar_hip.h SONAR_Q_*), or the
+    replace* parameters (count, flip, sign_mode).  ``per_row`` strategies reduce along ``dim`` a second time (the reference calls
+    ``max`` / ``median`` / ``mode`` with ``dim``, which refuses ``dim=None``)."""
+
+    __slots__ = ("name", "op", "replace", "per_row")
+
+    def __init__(self, name: str, op: int = 0, replace: Optional[tuple] = None, per_row: bool = False):
+        self.name, self.op, self.replace, self.per_row = name, op, replace, per_row
+
+    def __repr__(self):
+        return f"QuantileStrategy({self.name!r})"
+
+
+def _quantile_strategies() -> dict:
+    out = {}
+
+    def add(name, *args, **kw):
+        out[name] = QuantileStrategy(name, *args, **kw)
+
+    def waves(fn_name, cos_flag):
+        for wrong in (False, True):
+            stem = f"{fn_name}_wrong" if wrong else fn_name
+            for suffix, flag in (("", 0), ("_wholepi", hip_lib.Q_WAVE_WHOLEPI), ("_keepsign", hip_lib.Q_WAVE_KEEPSIGN)):
+                add(stem + suffix, hip_lib.Q_WAVE | cos_flag | flag | (hip_lib.Q_WAVE_WRONG if wrong else 0))
+
+    add("clamp", hip_lib.Q_CLAMP)
+    add("scale_down", hip_lib.Q_SCALE_DOWN, per_row=True)
+    add("tanh", hip_lib.Q_TANH)
+    add("tanh_outliers", hip_lib.Q_TANH_OUTLIERS)
+    add("sigmoid_keepsign", hip_lib.Q_SIGMOID_KEEPSIGN)
+    add("sigmoid", hip_lib.Q_SIGMOID)
+    add("sigmoid_outliers", hip_lib.Q_SIGMOID_OUTLIERS)
+    waves("sin", 0)
+    waves("cos", hip_lib.Q_WAVE_COS)
+    add("atan", hip_lib.Q_ATAN)
+    add("tenth", hip_lib.Q_TENTH)
+    add("half", hip_lib.Q_HALF)
+    add("zero", hip_lib.Q_ZERO)
+    add("reverse_zero", hip_lib.Q_REVERSE_ZERO)
+    add("mean", hip_lib.Q_MEAN)
+    add("median", hip_lib.Q_MEDIAN, per_row=True)
+    add("mode_1dec", hip_lib.Q_MODE_1DEC, per_row=True)
+    add("mode_2dec", hip_lib.Q_MODE_2DEC, per_row=True)
+    for count in (1, 2, 3):
+        stem = "replace" if count == 1 else f"replace_{count}pt"
+        for flip in ((False,) if count == 1 else (False, True)):
+            for sign_mode, suffix in ((0, ""), (1, "_keepsign"), (2, "_avoidsign")):
+                add(stem + ("_flip" if flip else "") + suffix, replace=(count, flip, sign_mode))
+    order = ("clamp", "scale_down", "tanh", "tanh_outliers", "sigmoid_keepsign", "sigmoid", "sigmoid_outliers", "sin", "sin_wholepi",
+             "sin_keepsign", "sin_wrong", "sin_wrong_wholepi", "sin_wrong_keepsign", "cos", "cos_wholepi", "cos_keepsign", "cos_wrong",
+             "cos_wrong_wholepi", "cos_wrong_keepsign", "atan", "tenth", "half", "zero", "reverse_zero", "mean", "median", "mode_1dec",
+             "mode_2dec", "replace", "replace_keepsign", "replace_avoidsign", "replace_2pt", "replace_3pt", "replace_2pt_flip",
+             "replace_3pt_flip", "replace_2pt_keepsign", "replace_3pt_keepsign", "replace_2pt_flip_keepsign", "replace_3pt_flip_keepsign",
+             "replace_2pt_avoidsign", "replace_3pt_avoidsign", "replace_2pt_flip_avoidsign", "replace_3pt_flip_avoidsign")
+    assert sorted(order) == sorted(out)
+    return {k: out[k] for k in order}
+
+
+# the reference's 43 strategies, in its order (the node dropdown is tuple(quantile_handlers.keys()))
+quantile_handlers = _quantile_strategies()
+
+
+def _quantile_check_dim(nd: int, dim: Optional[int], flatten: bool) -> None:
+    """What the reference's torch calls raise for this dim (flatten(start_dim=None), a dim out of range)."""
+    if nd > 1 and flatten and dim is None:
+        raise TypeError("flatten(): argument 'start_dim' must be int, not NoneType")
+    nd1 = max(nd, 1)
+    if dim is not None and not -nd1 <= dim < nd1:
+        raise IndexError(f"Dimension out of range (expected to be in range of [{-nd1}, {nd1 - 1}], but got {dim})")
+
+
+def _quantile_layout(noise: Tensor, dim: Optional[int], flatten: bool):
+    """(rows tensor with contiguous rows, rows, inner, inverse permutation or None, row length along the original layout, stride of a row's
+    values in the original layout).  Raises what the reference's torch calls raise for the same arguments."""
+    nd = noise.ndim
+    _quantile_check_dim(nd, dim, flatten)
+    if nd > 1 and flatten:
+        d = dim % nd
+        inner = 1
+        for s in noise.shape[d:]:
+            inner *= s
+        return noise.contiguous(), noise.numel() // inner, inner, None, inner, 1
+    if dim is None:
+        return noise.contiguous(), 1, noise.numel(), None, noise.numel(), 1
+    if nd == 0:
+        return noise.reshape(1).contiguous(), 1, 1, None, 1, 1
+    d = dim % nd
+    length = noise.shape[d]
+    stride = 1
+    for s in noise.shape[d + 1:]:
+        stride *= s
+    rows_last, inverse = dims_last(noise, [d])
+    return rows_last, noise.numel() // length, length, inverse, length, stride
+
+
+def _quantile_once(noise: Tensor, q: float, dim, flatten: bool, nq_fac: float, pow_fac: float, strategy: QuantileStrategy, eps: float) -> Tensor:
+    from . import noise_generation
+
+    _quantile_check_dim(noise.ndim, dim, flatten)
+    if strategy.per_row and dim is None:
+        raise RuntimeError("Please look up dimensions by name, got: name = None.")
+    _require_device(noise, "quantile_normalize")
+    x = noise if noise.dtype == torch.float32 else noise.to(torch.float32)
+    rows_t, rows, inner, inverse, length, stride = _quantile_layout(x, dim, flatten)
+    across = dim is None or strategy.replace is not None or dim % max(x.ndim, 1) == 0  # reductions that mix the batch's samples
+    if across and noise_generation.current_batch_offset() != 0:
+        raise NotImplementedError("quantile_normalize: this dim / strategy reduces across the samples of the batch, which a sharded batch "
+                                  "splits (reduce on one rank, or use a per-sample dim)")
+    centered = q < 0
+    aq = abs(q)
+    if strategy.replace is None:
+        out = torch.empty_like(rows_t)
+        hip_lib.quantile_rows(rows_t, rows, inner, aq, nq_fac, eps, strategy.op, centered, pow_fac, out)
+        out = dims_restore(out, inverse)
+    else:
+        stats = hip_lib.quantile_rows(rows_t, rows, inner, aq, nq_fac, eps, hip_lib.Q_CLAMP, centered, pow_fac, None)
+        src = x.contiguous()
+        out = torch.empty_like(src)
+        count, flip, sign_mode = strategy.replace
+        if hip_lib.quantile_replace(src, stats, length, stride, centered, count, flip, sign_mode, pow_fac, out) == 0:
+            raise RuntimeError("ZeroDivisionError")  # the reference's `arange(n) % n_candidates` with no candidate
+    out = out.reshape(noise.shape)
+    return out if noise.dtype == torch.float32 else out.to(noise.dtype)
+
+
+def quantile_normalize(noise: Tensor, *, quantile=0.75, dim: Optional[int] = 1, flatten: bool = True, nq_fac: float = 1.0,
+                       pow_fac: float = 0.5, strategy: str = "clamp", strategy_handler=None, eps: float = 1e-08) -> Tensor:
+    """py/utils.py:367-449 on the device: per-row |x| quantile (radix select), one of ``quantile_handlers``, the "centered" mapping for a
+    negative quantile and the sign-preserving power.  Returns a new tensor (the input is left as it is), or ``noise`` itself where the
+    reference returns early.  Unlike torch.quantile, rows of more than 2^24 values are fine."""
+    if noise.numel() == 0:
+        return noise
+    if isinstance(quantile, (tuple, list)):
+        for q in quantile:
+            noise = quantile_normalize(noise, quantile=q, dim=dim, flatten=flatten, nq_fac=nq_fac, pow_fac=pow_fac, strategy=strategy,
+                                       strategy_handler=strategy_handler)
+        return noise
+    if quantile is None or quantile >= 1 or quantile <= -1:
+        return noise
+    if strategy_handler is not None:
+        raise NotImplementedError("quantile_normalize: a Python strategy_handler would run on the host; only the built-in strategies run here")
+    if noise.ndim > 1 and flatten and dim is None:
+        raise TypeError("flatten(): argument 'start_dim' must be int, not NoneType")
+    handler = quantile_handlers.get(strategy)
+    if handler is None:
+        raise ValueError("Unknown strategy")
+    return _quantile_once(noise, float(quantile), dim, flatten, float(nq_fac), float(pow_fac), handler, float(eps))

@@ -137,6 +137,53 @@ int sonar_studentt_f32(float* x, const float* gamma, float loc, float scale, flo
 int sonar_abs_quantile_rows_f32(const float* x, int64_t rows, int64_t inner, int64_t rank_lo, float rank_frac, float* out,
                                 void* stream);
 int sonar_clamp_signpow_rows_f32(float* x, int64_t rows, int64_t inner, const float* limit, float mul, float p, void* stream);
+/* Quantile filtering (utils.quantile_normalize, py/utils.py:123-449).  Rows are `inner` contiguous values.
+ *  sonar_quantile_rows_ws_bytes  bytes of workspace sonar_quantile_rows_f32 needs for this shape and strategy (0: none)
+ *  sonar_quantile_rows_f32   per row: nq = quantile(|p|, q) * nq_fac + eps (linear interpolation, the caller passes the fp32 rank
+ *                            q*(inner-1) as rank_lo + rank_frac), p = x, or sign(x) * (max|x| - |x|) when centered = 1; then the
+ *                            strategy `op` (SONAR_Q_*, the wave strategies as SONAR_Q_WAVE | SONAR_Q_WAVE_* flags), the centered
+ *                            back-mapping sign(o) * (max|x| - |o|) and copysign(|o|^pow_fac, o) unless pow_fac is 0 or 1.  out (may be
+ *                            NULL: statistics only) must not alias x.  stats receives [rows][3] = (nq, max|x|, second statistic: nq / max|p|
+ *                            for scale_down, the mean, the lower median or the mode).  Rows of up to 65536 values are read once, one
+ *                            workgroup per row; longer rows are split across workgroups (per-pass global histograms in `ws`), except
+ *                            for the mode.  The mode is taken over the row's finite values.
+ *  sonar_quantile_replace_ws_elems     int64 elements of the `counts` workspace for n values
+ *  sonar_quantile_replace_compact_f32  the replace* candidates: the values p with |p| <= nq of their row, over the whole tensor in
+ *                            memory order, into cand[n]; counts[ws - 1] = their number.  Value i belongs to statistics row
+ *                            (i / (len * stride)) * stride + i % stride (stats as written by sonar_quantile_rows_f32)
+ *  sonar_quantile_replace_apply_f32    out[j] = p[j] where |p[j]| <= nq, else the mean over k < count of
+ *                            cand[((j - s_k) mod n) mod n_cand], s_k = k (-k for odd k when flip), then copysign toward p (sign_mode 1)
+ *                            or -p (2), the centered back-mapping and the power.  Writes nothing when n_cand is 0. */
+#define SONAR_Q_CLAMP 0
+#define SONAR_Q_TANH 1
+#define SONAR_Q_TANH_OUTLIERS 2
+#define SONAR_Q_SIGMOID 3
+#define SONAR_Q_SIGMOID_KEEPSIGN 4
+#define SONAR_Q_SIGMOID_OUTLIERS 5
+#define SONAR_Q_ATAN 6
+#define SONAR_Q_TENTH 7
+#define SONAR_Q_HALF 8
+#define SONAR_Q_ZERO 9
+#define SONAR_Q_REVERSE_ZERO 10
+#define SONAR_Q_SCALE_DOWN 11
+#define SONAR_Q_MEAN 12
+#define SONAR_Q_MEDIAN 13
+#define SONAR_Q_MODE_1DEC 14
+#define SONAR_Q_MODE_2DEC 15
+#define SONAR_Q_WAVE 16
+#define SONAR_Q_WAVE_COS 0x100
+#define SONAR_Q_WAVE_WHOLEPI 0x200
+#define SONAR_Q_WAVE_WRONG 0x400
+#define SONAR_Q_WAVE_KEEPSIGN 0x800
+int64_t sonar_quantile_rows_ws_bytes(int64_t rows, int64_t inner, int op);
+int sonar_quantile_rows_f32(const float* x, int64_t rows, int64_t inner, int64_t rank_lo, float rank_frac, float nq_fac, float eps, int op,
+                            int centered, float pow_fac, float* out, float* stats, void* ws, void* stream);
+int64_t sonar_quantile_replace_ws_elems(int64_t n);
+int sonar_quantile_replace_compact_f32(const float* x, const float* stats, int64_t n, int64_t len, int64_t stride, int centered,
+                                       float* cand, int64_t* counts, void* stream);
+int sonar_quantile_replace_apply_f32(const float* x, const float* stats, int64_t n, int64_t len, int64_t stride, int centered,
+                                     const float* cand, const int64_t* counts, int count, int flip, int sign_mode, float pow_fac, float* out,
+                                     void* stream);
 /* RippleFilteredNoise, py/noise.py:1197-1200: x[i] *= table[(i / inner) % len] (a sin / cos gain profile along one dimension, or along
  * the flattened trailing dimensions with inner = 1); follow_sign: the result takes the sign of 1 - table[..] (torch.copysign). In place. */
 int sonar_mul_table_f32(float* x, const float* table, int64_t n, int64_t inner, int64_t len, int follow_sign, void* stream);
