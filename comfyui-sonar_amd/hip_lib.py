@@ -54,6 +54,21 @@ class MomentumCfg(C.Structure):
     ]
 
 
+class DistroParams(C.Structure):
+    """Mirror of ``sonar_distro_params`` (include/sonar_hip.h)."""
+
+    _fields_ = [
+        ("family", C.c_int32),
+        ("k", C.c_int32),
+        ("row", C.c_int32),
+        ("col", C.c_int32),
+        ("a", C.c_float),
+        ("b", C.c_float),
+        ("c", C.c_float),
+        ("v", C.c_float * 16),
+    ]
+
+
 _P = C.c_void_p
 _I64 = C.c_int64
 _U64 = C.c_uint64
@@ -144,6 +159,7 @@ SIGNATURES = {
     "sonar_quantile_replace_apply_f32": (_I, [_P, _P, _I64, _I64, _I64, _I, _P, _P, _I, _I, _I, _F, _P, _P]),
     "sonar_mul_table_f32": (_I, [_P, _P, _I64, _I64, _I64, _I, _P]),
     "sonar_laplace_add_f32": (_I, [_P, _P, _F, _F, _F, _I64, _P]),
+    "sonar_distro_fill_f32": (_I, [_P, _I64, _U64, _U64, _I64, C.POINTER(DistroParams), _P]),
     "sonar_power_plane_kind": (_I, [_I64, _I64]),
     "sonar_power_block_ws_bytes": (_I64, [_I64, _I64, _I64]),
     "sonar_power_block_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _U64, _U64, _I64, _I, _I, _F, _F, _P, _P]),
@@ -552,6 +568,27 @@ def laplace_add_(x: torch.Tensor, u: torch.Tensor, div_fac: float, loc: float, s
     _check(load().sonar_laplace_add_f32(_dev(x, "x"), _dev(u, "u"), float(div_fac), float(loc), float(scale), x.numel(), _stream()),
            "sonar_laplace_add_f32")
     return x
+
+
+# family codes of sonar_distro_fill_f32 (include/sonar_hip.h SONAR_DISTRO_*), in the reference's table order
+(DISTRO_EXPONENTIAL, DISTRO_CAUCHY, DISTRO_GEOMETRIC, DISTRO_LOG_NORMAL, DISTRO_NORMAL, DISTRO_BETA, DISTRO_CONTINUOUS_BERNOULLI, DISTRO_DIRICHLET,
+ DISTRO_FISHER_SNEDECOR, DISTRO_GAMMA, DISTRO_GUMBEL, DISTRO_INVERSE_GAMMA, DISTRO_KUMARASWAMY, DISTRO_LAPLACIAN, DISTRO_LKJCHOLESKY,
+ DISTRO_LRMVARIATE_NORMAL, DISTRO_MVARIATE_NORMAL, DISTRO_PARETO, DISTRO_POISSON, DISTRO_RELAXED_BERNOULLI, DISTRO_RELAXED_ONEHOTCATEGORICAL,
+ DISTRO_STUDENTT, DISTRO_UNIFORM, DISTRO_VONMISES, DISTRO_WEIBULL, DISTRO_WISHART) = range(26)
+DISTRO_MAX_EVENT, DISTRO_MAX_PROPOSALS, DISTRO_DOMAIN = 16, 64, 0x44495354
+
+
+def distro_fill(shape, device, seed: int, stream_id: int, elem_offset: int, family: int, *, k: int = 0, row: int = 0, col: int = 0,
+                a: float = 0.0, b: float = 0.0, c: float = 0.0, v: Sequence[float] = ()) -> torch.Tensor:
+    """sonar_distro_fill_f32: a new tensor of ``shape``, every element the selected component of one draw of ``family``."""
+    if len(v) > DISTRO_MAX_EVENT:
+        raise SonarHipError(f"distro_fill: at most {DISTRO_MAX_EVENT} event parameters (got {len(v)})")
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    p = DistroParams(int(family), int(k), int(row), int(col), float(a), float(b), float(c), (C.c_float * 16)(*[float(x) for x in v]))
+    _check(load().sonar_distro_fill_f32(_dev(out, "out"), out.numel(), seed & (2**64 - 1), int(stream_id), int(elem_offset), C.byref(p),
+                                        _stream()),
+           "sonar_distro_fill_f32")
+    return out
 
 
 def powerlaw_(x: torch.Tensor, alpha: float, use_sign: bool) -> torch.Tensor:

@@ -450,6 +450,17 @@ class AdvancedPowerLawNoise(AdvancedNoiseBase):
         return PowerLawNoiseGenerator
 
 
+class AdvancedDistroNoise(AdvancedNoiseBase):
+    """py/noise.py:316-329."""
+
+    ns_factory_arg_keys = ("distro", "quantile_norm", "quantile_norm_dim", "quantile_norm_flatten", "result_index",
+                           *DistroNoiseGenerator.build_params().keys())
+
+    @property
+    def ns_factory(self):
+        return DistroNoiseGenerator
+
+
 # --------------------------------------------------------------------------------------------------
 def _prep_mask(mask: Tensor, x: Tensor) -> Tensor:
     """py/noise.py:516-522: bilinear-resize the mask to the latent size, repeat to the batch."""

@@ -850,10 +850,218 @@ def _off_path(type_name: str):
     return _OffPath
 
 
-DistroNoiseGenerator = _off_path("distro")
 VoronoiNoiseGenerator = _off_path("voronoi")
 CollatzNoiseGenerator = _off_path("collatz")
 ScatternetFilteredNoiseGenerator = _off_path("scatternet_filtered")
+
+
+def _lowrank_mvn(loc, cov_factor, cov_diag):
+    return torch.distributions.LowRankMultivariateNormal(loc=loc, cov_factor=cov_factor.reshape(loc.numel(), -1), cov_diag=cov_diag)
+
+
+def _mvn(loc, cov_multiplier=1.0):
+    return torch.distributions.MultivariateNormal(loc=loc, covariance_matrix=torch.eye(loc.numel(), dtype=loc.dtype).mul_(cov_multiplier))
+
+
+def _wishart(df, cov_size=2, cov_multiplier=1.0):
+    return torch.distributions.Wishart(df=df, covariance_matrix=torch.eye(int(cov_size), dtype=df.dtype).mul_(cov_multiplier))
+
+
+def trim_result_index(noise: Tensor, ndim: int, result_index) -> Tensor:
+    """py/noise_generation.py:1165-1182: while ``noise`` has more than ``ndim`` dimensions, index its last one with
+    result_index[t % len] (negative counts from the end, out of range clamps).  A bare value is a one-element list; elements are
+    compared with 0 as they are (a string raises TypeError)."""
+    if noise.ndim <= ndim:
+        return noise
+    if not isinstance(result_index, (tuple, list)):
+        result_index = (result_index,)
+    if len(result_index) == 0:
+        raise ValueError("When result_index is a list, it must not be empty")
+    t = 0
+    while noise.ndim > ndim:
+        idx = result_index[t % len(result_index)]
+        if idx < 0:
+            idx = noise.shape[-1] + idx
+        noise = noise[..., max(0, min(noise.shape[-1] - 1, idx))]
+        t += 1
+    return noise
+
+
+class DistroNoiseGenerator(NoiseGenerator):
+    """py/noise_generation.py:805-1256: one draw of a torch.distributions family per element, ``result_index`` picking one component
+    where the family adds batch or event dimensions, then ``utils.quantile_normalize``.  The distribution object is always built on the
+    host from the parsed parameters (torch's own validation and refusals, and the trailing shape result_index selects from).  Replay mode
+    draws from it on the host generator as the reference does; generate mode launches sonar_distro_fill_f32 for the selected component
+    (csrc/distro.hip), never forming the trailing dimensions on the device."""
+
+    name = "distro"
+    SIMPLE = frozenset(("exponential", "cauchy", "geometric", "log_normal", "normal"))  # Tensor methods on an empty(shape): scalar params
+    # name -> (tensor method or distribution constructor, ((parameter, default), ...)); defaults typed as the node's sockets
+    FAMILIES = {
+        "exponential": (Tensor.exponential_, (("lambd", 1.0),)),
+        "cauchy": (Tensor.cauchy_, (("median", "0.0"), ("sigma", 1.0))),
+        "geometric": (Tensor.geometric_, (("p", 0.25),)),
+        "log_normal": (Tensor.log_normal_, (("mean", 1.0), ("std", 2.0))),
+        "normal": (Tensor.normal_, (("mean", 0.0), ("std", 1.0))),
+        "beta": (torch.distributions.Beta, (("concentration0", "0.5"), ("concentration1", "0.5"))),
+        "continuous_bernoulli": (torch.distributions.ContinuousBernoulli, (("probs", "0.5"),)),
+        "dirichlet": (torch.distributions.Dirichlet, (("concentration", "0.5 0.5"),)),
+        "fisher_snedecor": (torch.distributions.FisherSnedecor, (("df1", "1.0"), ("df2", "2.0"))),
+        "gamma": (torch.distributions.Gamma, (("concentration", "1.0"), ("rate", "1.0"))),
+        "gumbel": (torch.distributions.Gumbel, (("loc", "1.0"), ("scale", "2.0"))),
+        "inverse_gamma": (torch.distributions.InverseGamma, (("concentration", "1.0"), ("rate", "1.0"))),
+        "kumaraswamy": (torch.distributions.Kumaraswamy, (("concentration0", "1.0"), ("concentration1", "1.0"))),
+        "laplacian": (torch.distributions.Laplace, (("loc", "0.0"), ("scale", "1.0"))),
+        "lkjcholesky": (torch.distributions.LKJCholesky, (("dim", 3), ("concentration", "1.0"))),
+        "lrmvariate_normal": (_lowrank_mvn, (("loc", "0.0 0.0"), ("cov_factor", "1.0 0.0"), ("cov_diag", "1.0 1.0"))),
+        "mvariate_normal": (_mvn, (("loc", "0.0 0.0"), ("cov_multiplier", 1.0))),
+        "pareto": (torch.distributions.Pareto, (("scale", "1.0"), ("alpha", "1.0"))),
+        "poisson": (torch.distributions.Poisson, (("rate", "1.5"),)),
+        "relaxed_bernoulli": (torch.distributions.RelaxedBernoulli, (("temperature", 0.75), ("probs", "0.66"))),
+        "relaxed_onehotcategorical": (torch.distributions.RelaxedOneHotCategorical, (("temperature", 1.5), ("probs", "0.33 0.66"))),
+        "studentt": (torch.distributions.StudentT, (("loc", "0.0"), ("scale", "1.0"), ("df", "1.0"))),
+        "uniform": (torch.distributions.Uniform, (("low", 0.0), ("high", 1.0))),
+        "vonmises": (torch.distributions.VonMises, (("loc", "1.0"), ("concentration", "1.0"))),
+        "weibull": (torch.distributions.Weibull, (("scale", "1.0"), ("concentration", "1.0"))),
+        "wishart": (_wishart, (("df", "2.0"), ("cov_size", 2), ("cov_multiplier", 1.0))),
+    }
+    MAX_MATRIX_DIM = 8  # lkjcholesky / wishart kernels are instantiated for d in 2..8
+
+    def __init__(self, x, **kwargs):
+        super().__init__(x, **kwargs)
+        if self.distro not in self.FAMILIES:
+            raise ValueError("Bad distro")
+
+    @classmethod
+    def build_params(cls):
+        return {f"{fam}_{name}": default for fam, (_fun, params) in cls.FAMILIES.items() for name, default in params}
+
+    @classmethod
+    def ng_params(cls):
+        return super().ng_params() | {"distro": "normal", "quantile_norm": 0.85, "quantile_norm_flatten": True, "quantile_norm_dim": 1,
+                                      "quantile_norm_pow": 0.5, "quantile_norm_fac": 1.0, "result_index": "-1"} | cls.build_params()
+
+    @staticmethod
+    def _param(val, simple_fun):
+        """py/noise_generation.py:1197-1215 (tensors on the host)."""
+        if isinstance(val, Tensor):
+            return simple_fun(val) if simple_fun is not None else val
+        if isinstance(val, str):
+            val = tuple(float(v) for v in val.split(None))
+        if simple_fun is not None:
+            if isinstance(val, (float, int)):
+                return simple_fun(val)
+            if len(val) > 1:
+                raise ValueError("Couldn't return result as float")
+            return simple_fun(val[0])
+        if not isinstance(val, (tuple, list)):
+            val = (val,)
+        return torch.tensor(val, dtype=torch.float32)
+
+    def distro_kwargs(self):
+        fam = self.distro
+        simple = fam in self.SIMPLE
+        return {k: self._param(getattr(self, f"{fam}_{k}"), int if k == "dim" else float if simple else None) for k, _ in self.FAMILIES[fam][1]}
+
+    def generate(self, *_args):
+        fun, _ = self.FAMILIES[self.distro]
+        kwargs = self.distro_kwargs()
+        simple = self.distro in self.SIMPLE
+        shape = tuple(self.shape)
+        if simple:
+            if self.cpu:
+                noise = fun(torch.empty(shape, dtype=torch.float32), **kwargs)
+            else:
+                fun(torch.empty(1), generator=torch.Generator(), **kwargs)  # torch's refusals, without touching the global generator
+            dobj, trailing = None, ()
+        else:
+            dobj = fun(**kwargs)
+            trailing = tuple(dobj.batch_shape + dobj.event_shape)
+            if self.cpu:
+                noise = (dobj.rsample if getattr(dobj, "has_rsample", False) else dobj.sample)(shape)
+        if self.cpu:
+            noise = tensor_to(trim_result_index(noise, len(shape), self.result_index).contiguous(), self.device)
+        else:
+            flat = int(trim_result_index(torch.arange(math.prod(trailing)).reshape(trailing), 0, self.result_index))
+            noise = self._device_draw(dobj, kwargs, torch.unravel_index(torch.tensor(flat), trailing) if trailing else ())
+        return utils.quantile_normalize(noise, quantile=self.quantile_norm, dim=self.quantile_norm_dim, flatten=self.quantile_norm_flatten,
+                                        nq_fac=self.quantile_norm_fac, pow_fac=self.quantile_norm_pow).reshape(shape).contiguous()
+
+    def kernel_params(self, dobj, kwargs, index) -> dict:
+        """Arguments of hip_lib.distro_fill for the component at ``index`` (batch then event indices) of the family's trailing shape."""
+        fam = self.distro
+        if dobj is None:
+            vals = [float(v) for v in kwargs.values()]
+            return {"family": getattr(hip_lib, f"DISTRO_{fam.upper()}"), **dict(zip("ab", vals))}
+        nb = len(dobj.batch_shape)
+        bidx, eidx = tuple(int(i) for i in index[:nb]), tuple(int(i) for i in index[nb:])
+
+        def at(t, event=()):
+            return torch.as_tensor(t, dtype=torch.float64).broadcast_to(tuple(dobj.batch_shape) + tuple(event))[bidx]
+
+        def f(t):
+            return float(at(t))
+
+        k = int(dobj.event_shape[0]) if len(dobj.event_shape) else 0
+        if k > hip_lib.DISTRO_MAX_EVENT and fam not in ("lkjcholesky", "wishart"):
+            raise NotImplementedError(f"distro {fam}: device draws take at most {hip_lib.DISTRO_MAX_EVENT} components (got {k}); use cpu noise")
+        if fam in ("lkjcholesky", "wishart") and not 2 <= k <= self.MAX_MATRIX_DIM:
+            raise NotImplementedError(f"distro {fam}: device draws take d in 2..{self.MAX_MATRIX_DIM} (got {k}); use cpu noise")
+        p = {"family": getattr(hip_lib, f"DISTRO_{fam.upper()}")}
+        if fam in ("beta", "kumaraswamy"):
+            p.update(a=f(dobj.concentration1), b=f(dobj.concentration0))
+        elif fam == "continuous_bernoulli":
+            p.update(a=f(dobj.probs))
+        elif fam == "dirichlet":
+            p.update(k=k, row=eidx[0], v=at(dobj.concentration, dobj.event_shape).tolist())
+        elif fam == "fisher_snedecor":
+            p.update(a=f(dobj.df1), b=f(dobj.df2))
+        elif fam in ("gamma", "inverse_gamma"):
+            p.update(a=f(dobj.concentration), b=f(dobj.rate))
+        elif fam in ("gumbel", "laplacian"):
+            p.update(a=f(dobj.loc), b=f(dobj.scale))
+        elif fam == "lkjcholesky":
+            p.update(k=k, row=eidx[0], col=eidx[1], a=f(dobj.concentration))
+        elif fam == "lrmvariate_normal":
+            w = at(dobj.cov_factor, tuple(dobj.cov_factor.shape[-2:]))[eidx[0]]
+            if w.numel() > hip_lib.DISTRO_MAX_EVENT:
+                raise NotImplementedError(f"distro {fam}: device draws take a rank of at most {hip_lib.DISTRO_MAX_EVENT}; use cpu noise")
+            p.update(k=w.numel(), row=eidx[0], a=float(at(dobj.loc, dobj.event_shape)[eidx[0]]),
+                     b=math.sqrt(float(at(dobj.cov_diag, dobj.event_shape)[eidx[0]])), v=w.tolist())
+        elif fam == "mvariate_normal":
+            p.update(row=eidx[0], a=float(at(dobj.loc, dobj.event_shape)[eidx[0]]),
+                     b=float(at(dobj.scale_tril, dobj.event_shape * 2)[eidx[0], eidx[0]]))
+        elif fam == "pareto":
+            p.update(a=f(dobj.scale), b=f(dobj.alpha))
+        elif fam == "poisson":
+            p.update(a=f(dobj.rate))
+        elif fam == "relaxed_bernoulli":
+            p.update(a=f(dobj.logits), b=f(dobj.temperature))
+        elif fam == "relaxed_onehotcategorical":
+            p.update(k=k, row=eidx[0], a=float(at(dobj.temperature, dobj.event_shape)[eidx[0]]), v=at(dobj.logits, dobj.event_shape).tolist())
+        elif fam == "studentt":
+            p.update(a=f(dobj.loc), b=f(dobj.scale), c=f(dobj.df))
+        elif fam == "uniform":
+            p.update(a=f(dobj.low), b=f(dobj.high))
+        elif fam == "vonmises":
+            kappa = f(dobj.concentration)  # torch's _proposal_r, in double
+            tau = 1.0 + math.sqrt(1.0 + 4.0 * kappa * kappa)
+            rho = (tau - math.sqrt(2.0 * tau)) / (2.0 * kappa)
+            p.update(a=f(dobj.loc), b=kappa, c=1.0 / kappa + kappa if kappa < 1e-5 else (1.0 + rho * rho) / (2.0 * rho))
+        elif fam == "weibull":
+            p.update(a=f(dobj.scale), b=f(dobj.concentration))
+        elif fam == "wishart":
+            p.update(k=k, row=eidx[0], col=eidx[1], a=f(dobj.df), b=float(at(dobj.covariance_matrix, dobj.event_shape)[0, 0]))
+        return p
+
+    def _device_draw(self, dobj, kwargs, index) -> Tensor:
+        p = self.kernel_params(dobj, kwargs, index)
+        vals = [p.get(k, 0.0) for k in ("a", "b", "c")] + list(p.get("v", ()))
+        if not all(math.isfinite(v) for v in vals):
+            raise ValueError(f"distro {self.distro}: non-finite parameter")
+        seed, stream = self.device_key()
+        shape = tuple(self.shape)
+        return hip_lib.distro_fill(shape, self.device, seed, stream, self.latent_elem_offset(math.prod(shape[1:])), **p)
 
 
 class PowerLawNoiseGenerator(NoiseGenerator):

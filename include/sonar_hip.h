@@ -184,6 +184,59 @@ int sonar_quantile_replace_compact_f32(const float* x, const float* stats, int64
 int sonar_quantile_replace_apply_f32(const float* x, const float* stats, int64_t n, int64_t len, int64_t stride, int centered,
                                      const float* cand, const int64_t* counts, int count, int flip, int sign_mode, float pow_fac, float* out,
                                      void* stream);
+/* Distro noise (DistroNoiseGenerator, py/noise_generation.py:805-1256), generate mode.  sonar_distro_fill_f32 writes out[i], i < n, as
+ * the selected component of one draw of `family` (SONAR_DISTRO_*) for global element elem_offset + i: the host has already applied
+ * result_index and passes the selected component's parameters in `p`.  Every value is a pure function of (seed, stream_id, global element
+ * index): Philox4x32-10 blocks with key (seed_lo, seed_hi ^ SONAR_DISTRO_DOMAIN) and counter (idx_lo, idx_hi | stream_hi << 16, block,
+ * stream_lo), so idx and stream_id must be below 2^48.  Block allotment and word conversions: INTEGRATION.md 3b.  Rejection samplers stop
+ * after SONAR_DISTRO_MAX_PROPOSALS proposals with a finite fallback.  Parameters must be finite and inside the family's support (the
+ * host validates them through torch).  Event families take k <= 16; lkjcholesky and wishart take d = k in 2..8.
+ * Fields of sonar_distro_params per family (a, b, c; v; k; row, col):
+ *   exponential (lambd)  cauchy (median, sigma)  geometric (p)  log_normal / normal (mean, std)  beta (concentration1, concentration0)
+ *   continuous_bernoulli (probs)  dirichlet (v = concentrations, k, row = component)  fisher_snedecor (df1, df2)
+ *   gamma / inverse_gamma (concentration, rate)  gumbel / laplacian (loc, scale)  kumaraswamy (concentration1, concentration0)
+ *   lkjcholesky (concentration; k = d; row, col)  lrmvariate_normal (loc, sqrt(cov_diag); v = cov_factor row, k = rank)
+ *   mvariate_normal (loc, sqrt(cov_multiplier))  pareto (scale, alpha)  poisson (rate)  relaxed_bernoulli (logit, temperature)
+ *   relaxed_onehotcategorical (temperature; v = logits, k, row = component)  studentt (loc, scale, df)  uniform (low, high)
+ *   vonmises (loc, concentration, proposal_r)  weibull (scale, concentration)  wishart (df, cov_multiplier; k = d; row, col) */
+#define SONAR_DISTRO_EXPONENTIAL 0
+#define SONAR_DISTRO_CAUCHY 1
+#define SONAR_DISTRO_GEOMETRIC 2
+#define SONAR_DISTRO_LOG_NORMAL 3
+#define SONAR_DISTRO_NORMAL 4
+#define SONAR_DISTRO_BETA 5
+#define SONAR_DISTRO_CONTINUOUS_BERNOULLI 6
+#define SONAR_DISTRO_DIRICHLET 7
+#define SONAR_DISTRO_FISHER_SNEDECOR 8
+#define SONAR_DISTRO_GAMMA 9
+#define SONAR_DISTRO_GUMBEL 10
+#define SONAR_DISTRO_INVERSE_GAMMA 11
+#define SONAR_DISTRO_KUMARASWAMY 12
+#define SONAR_DISTRO_LAPLACIAN 13
+#define SONAR_DISTRO_LKJCHOLESKY 14
+#define SONAR_DISTRO_LRMVARIATE_NORMAL 15
+#define SONAR_DISTRO_MVARIATE_NORMAL 16
+#define SONAR_DISTRO_PARETO 17
+#define SONAR_DISTRO_POISSON 18
+#define SONAR_DISTRO_RELAXED_BERNOULLI 19
+#define SONAR_DISTRO_RELAXED_ONEHOTCATEGORICAL 20
+#define SONAR_DISTRO_STUDENTT 21
+#define SONAR_DISTRO_UNIFORM 22
+#define SONAR_DISTRO_VONMISES 23
+#define SONAR_DISTRO_WEIBULL 24
+#define SONAR_DISTRO_WISHART 25
+#define SONAR_DISTRO_MAX_EVENT 16
+#define SONAR_DISTRO_MAX_PROPOSALS 64
+#define SONAR_DISTRO_DOMAIN 0x44495354u
+typedef struct sonar_distro_params {
+    int32_t family;
+    int32_t k;
+    int32_t row, col;
+    float a, b, c;
+    float v[SONAR_DISTRO_MAX_EVENT];
+} sonar_distro_params;
+int sonar_distro_fill_f32(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t elem_offset, const sonar_distro_params* p,
+                          void* stream);
 /* RippleFilteredNoise, py/noise.py:1197-1200: x[i] *= table[(i / inner) % len] (a sin / cos gain profile along one dimension, or along
  * the flattened trailing dimensions with inner = 1); follow_sign: the result takes the sign of 1 - table[..] (torch.copysign). In place. */
 int sonar_mul_table_f32(float* x, const float* table, int64_t n, int64_t inner, int64_t len, int follow_sign, void* stream);
