@@ -186,6 +186,9 @@ SIGNATURES = {
     "sonar_wcfg_bands_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _PD, _PD, _PD, _PD, _I, _I, _I, _PD, _D, _D, _D, _I, _P]),
     "sonar_wcfg_bands_f64": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _PD, _PD, _PD, _PD, _I, _I, _I, _PD, _D, _D, _D, _I, _P]),
     "sonar_minmax_rescale_f32": (_I, [_P, _I64, _I64, _P, _P, _F, _D, _D, _P, _P]),
+    "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
+    "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
+    "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
     "sonar_axis_taps_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _I, _P]),
     "sonar_axis_taps_f64": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _I, _P]),
     "sonar_dtcwt_q2c_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
@@ -1636,6 +1639,51 @@ def minmax_rescale(x: torch.Tensor, rows: int, inner: int, lo: torch.Tensor, hi:
     _check(load().sonar_minmax_rescale_f32(_dev(x, "x"), rows, inner, _dev(lo, "lo"), _dev(hi, "hi"), float(eps), float(target_min),
                                            float(target_max), _dev(out, "out"), _stream()), "sonar_minmax_rescale_f32")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ SonarNoiseImage
+IMAGE_BLEND_IDS = BLEND_IDS | {"simple_add": 3}  # SONAR_IMAGE_BLEND_ADD
+IMAGE_NPART, IMAGE_MAX_CHANNELS = 1024, 64       # SONAR_IMAGE_NPART, SONAR_IMAGE_MAX_CHANNELS
+
+
+def image_channel_mean(noise: torch.Tensor) -> torch.Tensor:
+    """``noise.mean(dim=1, keepdim=True)`` of an NCHW tensor (``sonar_image_channel_mean_f32``)."""
+    b, c, h, w = noise.shape
+    out = torch.empty((b, 1, h, w), dtype=torch.float32, device=noise.device)
+    _check(load().sonar_image_channel_mean_f32(_dev(noise, "noise"), b, c, h * w, _dev(out, "out"), _stream()), "sonar_image_channel_mean_f32")
+    return out
+
+
+def image_noise_compose(noise: torch.Tensor, image: Optional[torch.Tensor], shape, *, noise_lo: Optional[torch.Tensor] = None,
+                        noise_hi: Optional[torch.Tensor] = None, noise_min: float = 0.0, noise_max: float = 1.0, multiplier: float = 1.0,
+                        greyscale: bool = False, blend_mode: str = "simple_add", blend_strength: float = 0.5, channel_mask: int = 0,
+                        clamp: bool = True, eps: float = 1e-07):
+    """``sonar_image_noise_compose_f32``: NCHW ``noise`` ([B, C, H, W]; [B, 1, H, W] with ``greyscale``) composed into the NHWC ``image``
+    ([B, H, W, C] = ``shape``; None: zeros).  Returns the new NHWC image -- clipped to [0, 1] with ``clamp``, else unclipped together with
+    the per-sample (min, max) partial slots that ``image_rescale_`` consumes: (image, part_min, part_max)."""
+    b, h, w, c = (int(v) for v in shape)
+    if tuple(noise.shape) != (b, 1 if greyscale else c, h, w):
+        raise SonarHipError(f"image_noise_compose: noise {tuple(noise.shape)} does not fit the image {tuple(shape)}")
+    if image is not None and tuple(image.shape) != (b, h, w, c):
+        raise SonarHipError(f"image_noise_compose: image {tuple(image.shape)} is not {tuple(shape)}")
+    if (noise_lo is None) != (noise_hi is None) or (noise_lo is not None and (noise_lo.numel() != b or noise_hi.numel() != b)):
+        raise SonarHipError("image_noise_compose: noise_lo / noise_hi must both be given, one value per sample")
+    out = torch.empty((b, h, w, c), dtype=torch.float32, device=noise.device)
+    parts = None if clamp else torch.empty((2, b, IMAGE_NPART), dtype=torch.float32, device=noise.device)
+    _check(load().sonar_image_noise_compose_f32(
+        _dev(noise, "noise"), _opt(noise_lo, "noise_lo"), _opt(noise_hi, "noise_hi"), float(noise_min), float(noise_max), float(eps),
+        float(multiplier), int(bool(greyscale)), IMAGE_BLEND_IDS[blend_mode], float(blend_strength), int(channel_mask) & (2**64 - 1),
+        _opt(image, "image"), _dev(out, "out"), b, c, h * w, int(bool(clamp)), None if clamp else _dev(parts[0], "part_min"),
+        None if clamp else _dev(parts[1], "part_max"), _stream()), "sonar_image_noise_compose_f32")
+    return out if clamp else (out, parts[0], parts[1])
+
+
+def image_rescale_(image: torch.Tensor, part_min: torch.Tensor, part_max: torch.Tensor, eps: float = 1e-07) -> torch.Tensor:
+    """``normalize_to_scale(image, 0, 1)`` per sample of an NHWC image, in place, from the partial slots of ``image_noise_compose``."""
+    b, h, w, c = image.shape
+    _check(load().sonar_image_rescale_f32(_dev(image, "image"), b, c, h * w, _dev(part_min, "part_min"), _dev(part_max, "part_max"),
+                                          float(eps), _stream()), "sonar_image_rescale_f32")
+    return image
 
 
 def signed_rescale(x: torch.Tensor, rows: int, inner: int, min_neg: float, max_neg: float, min_pos: float, max_pos: float, eps: float = 1e-07) -> torch.Tensor:

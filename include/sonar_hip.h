@@ -237,6 +237,31 @@ typedef struct sonar_distro_params {
 } sonar_distro_params;
 int sonar_distro_fill_f32(float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t elem_offset, const sonar_distro_params* p,
                           void* stream);
+/* SonarNoiseImage (py/nodes/misc.py:158-357): noise composed into a ComfyUI IMAGE.  noise is NCHW ([batch][channels][plane], or
+ * [batch][1][plane] with greyscale != 0: the one plane serves every channel), image and out are NHWC ([batch][plane][channels]).
+ *  sonar_image_channel_mean_f32   out[b][p] = mean over c of noise[b][c][p] (channels added in order, true division): the greyscale fold
+ *                                 (:340), written as a plane so that its extremes can be reduced (sonar_minmax_rows_f32)
+ *  sonar_image_noise_compose_f32  per value, each step rounded on its own, in the reference's order (:341-352):
+ *                                   n = noise; with noise_lo / noise_hi (per-sample extremes, [batch]; both NULL: skipped)
+ *                                   n = clamp(((n - lo) / ((hi - lo) + eps)) * (noise_max - noise_min) + noise_min, noise_min, noise_max);
+ *                                   n *= multiplier; v = image (0 when image is NULL: pure noise);
+ *                                   bit c of channel_mask set: v = blend(v, n, blend_strength) (SONAR_BLEND_*, or SONAR_IMAGE_BLEND_ADD: v + n);
+ *                                   clamp != 0: out = clip(v, 0, 1); clamp == 0: out = v, and the (min, max) of every block's values go to
+ *                                   part_min / part_max ([batch][SONAR_IMAGE_NPART] each; slots no block owns are not written)
+ *                                 image must not overlap out.  One lane owns one pixel for 3 and 4 channels; any other count (<= 64) takes a plain
+ *                                 strided loop.
+ *  sonar_image_rescale_f32        normalize_to_scale(image, 0, 1) per sample (:350), in place on the NHWC image, the extremes taken from the
+ *                                 partial slots a clamp == 0 compose launch of the same (plane) wrote */
+#define SONAR_IMAGE_BLEND_ADD 3
+#define SONAR_IMAGE_NPART 1024
+#define SONAR_IMAGE_MAX_CHANNELS 64
+int sonar_image_channel_mean_f32(const float* noise, int64_t batch, int64_t channels, int64_t plane, float* out, void* stream);
+int sonar_image_noise_compose_f32(const float* noise, const float* noise_lo, const float* noise_hi, double noise_min, double noise_max,
+                                  float eps, float multiplier, int greyscale, int blend_mode, float blend_strength, uint64_t channel_mask,
+                                  const float* image, float* out, int64_t batch, int64_t channels, int64_t plane, int clamp,
+                                  float* part_min, float* part_max, void* stream);
+int sonar_image_rescale_f32(float* image, int64_t batch, int64_t channels, int64_t plane, const float* part_min, const float* part_max,
+                            float eps, void* stream);
 /* RippleFilteredNoise, py/noise.py:1197-1200: x[i] *= table[(i / inner) % len] (a sin / cos gain profile along one dimension, or along
  * the flattened trailing dimensions with inner = 1); follow_sign: the result takes the sign of 1 - table[..] (torch.copysign). In place. */
 int sonar_mul_table_f32(float* x, const float* table, int64_t n, int64_t inner, int64_t len, int follow_sign, void* stream);
