@@ -29,6 +29,8 @@ DWT_MODE_IDS = {"zero": 0, "symmetric": 1, "reflect": 2, "periodization": 3, "pe
 NPART = 1024
 BROWNIAN_MAX_TERMS = 96  # kMaxBrownianNodes (csrc/noise_gen.hip)
 ERR_ARG, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3  # include/sonar_hip.h
+DTYPE_IDS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # SONAR_DTYPE_* (the entry points that take a dtype code)
+CFG_BLEND_NONE = -1  # SONAR_CFG_BLEND_NONE
 
 
 class SonarHipError(RuntimeError):
@@ -189,6 +191,8 @@ SIGNATURES = {
     "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
+    "sonar_cfg_op_prepare": (_I, [_I, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _P]),
+    "sonar_cfg_op_finish": (_I, [_I, _P, _P, _P, _P, _I64, _P, _I, _F, _P, _I64, _I64, _P]),
     "sonar_axis_taps_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _I, _P]),
     "sonar_axis_taps_f64": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _I, _P]),
     "sonar_dtcwt_q2c_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
@@ -442,6 +446,67 @@ def to_d(x: torch.Tensor, denoised: torch.Tensor, sigma: float, out: Optional[to
     out = torch.empty_like(x) if out is None else out
     _check(load().sonar_scalar_op_f32(2, _dev(x, "x"), _dev(denoised, "denoised"), float(sigma), _dev(out, "out"), x.numel(), _stream()),
            "sonar_scalar_op_f32")
+    return out
+
+
+def _cfg_op_sigma(sigma: Optional[torch.Tensor], like: torch.Tensor, what: str):
+    """(pointer, sigma_n, inner) of the per-tensor or per-sample sigma of ``like`` ([batch, ...]); (None, 1, n or 1) without one."""
+    n = like.numel()
+    if sigma is None:
+        return None, 1, max(n, 1)
+    sn = sigma.numel()
+    batch = like.shape[0] if like.ndim else 1
+    if sn != 1 and sn != batch:
+        raise SonarHipError(f"{what}: {sn} sigmas for a batch of {batch}")
+    if n == 0:  # no sample to speak of: the call validates and launches nothing
+        return _dev(sigma, "sigma"), 1, 1
+    return _dev(sigma, "sigma"), sn, n // batch
+
+
+def cfg_op_prepare(x: Optional[torch.Tensor], t1: torch.Tensor, t2: Optional[torch.Tensor], sigma: Optional[torch.Tensor]):
+    """SonarApplyLatentOperationCFG before the operations, one launch: f(t) = (x - t) / sigma with a sigma (fp32 device tensor of one value
+    or one per sample; the prediction flip), f(t) = t without; returns fp32 (f(t1) - f(t2), f(t2)), or (f(t1), None) without t2.  x, t1
+    and t2 share one dtype (float32 / float16 / bfloat16) and are not written."""
+    dtype = t1.dtype
+    if dtype not in DTYPE_IDS:
+        raise SonarHipError(f"cfg_op_prepare: expected float32, float16 or bfloat16, got {dtype}")
+    for name, t in (("x", x if sigma is not None else None), ("t2", t2)):
+        if t is not None and t.shape != t1.shape:
+            raise SonarHipError(f"cfg_op_prepare: shape mismatch, {name} {tuple(t.shape)} vs t1 {tuple(t1.shape)}")
+    if sigma is not None and x is None:
+        raise SonarHipError("cfg_op_prepare: the flip needs x")
+    psigma, sigma_n, inner = _cfg_op_sigma(sigma, t1, "cfg_op_prepare")
+    result = torch.empty(t1.shape, dtype=torch.float32, device=t1.device)
+    t2_out = None if t2 is None else torch.empty_like(result)
+    _check(
+        load().sonar_cfg_op_prepare(DTYPE_IDS[dtype], None if sigma is None else _dev(x, "x", dtype), _dev(t1, "t1", dtype), _opt(t2, "t2", dtype),
+                                    psigma, sigma_n, _dev(result, "result"), _opt(t2_out, "t2_out"), t1.numel(), inner, _stream()),
+        "sonar_cfg_op_prepare",
+    )
+    return result, t2_out
+
+
+def cfg_op_finish(result: torch.Tensor, t2f: Optional[torch.Tensor], x: Optional[torch.Tensor], sigma: Optional[torch.Tensor],
+                  t1_orig: torch.Tensor, mode: Optional[str], w: float) -> torch.Tensor:
+    """... and after them, one launch: r = result + t2f; with a sigma r = x - sigma * r; returns blend(t1_orig, r, w) (``mode`` of
+    BLEND_IDS), or r for mode None / "none", as a new tensor of t1_orig's dtype.  result and t2f are the fp32 tensors of cfg_op_prepare."""
+    dtype = t1_orig.dtype
+    if dtype not in DTYPE_IDS:
+        raise SonarHipError(f"cfg_op_finish: expected float32, float16 or bfloat16, got {dtype}")
+    for name, t in (("t2f", t2f), ("x", x if sigma is not None else None), ("t1_orig", t1_orig)):
+        if t is not None and t.shape != result.shape:
+            raise SonarHipError(f"cfg_op_finish: shape mismatch, {name} {tuple(t.shape)} vs result {tuple(result.shape)}")
+    if sigma is not None and x is None:
+        raise SonarHipError("cfg_op_finish: the flip needs x")
+    blend_id = CFG_BLEND_NONE if mode is None or mode == "none" else BLEND_IDS[mode]
+    psigma, sigma_n, inner = _cfg_op_sigma(sigma, result, "cfg_op_finish")
+    out = torch.empty_like(t1_orig)
+    _check(
+        load().sonar_cfg_op_finish(DTYPE_IDS[dtype], _dev(result, "result"), _opt(t2f, "t2f"), None if sigma is None else _dev(x, "x", dtype),
+                                   psigma, sigma_n, _dev(t1_orig, "t1_orig", dtype), blend_id, float(w), _dev(out, "out", dtype),
+                                   result.numel(), inner, _stream()),
+        "sonar_cfg_op_finish",
+    )
     return out
 
 

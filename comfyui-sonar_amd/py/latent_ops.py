@@ -1,5 +1,6 @@
 """Sigma-gated latent operations (API of the reference's ``py/latent_ops.py``); the arithmetic (scale, difference, blend,
-noise add) runs through the HIP elementwise kernels."""
+noise add) runs through the HIP elementwise kernels.  ``LatentOperationCFG`` is the sampling-time patch that applies them
+(``SonarApplyLatentOperationCFG``, py/nodes/latent_operations.py:22-314)."""
 from __future__ import annotations
 
 import math
@@ -136,3 +137,122 @@ class SonarLatentOperationSetSeed(SonarLatentOperation):
             if saved is not None:
                 random.setstate(saved[0])
                 torch.random.set_rng_state(saved[1])
+
+
+# ------------------------------------------------------------------------------------------------ operations applied while sampling
+CFG_OP_MODES = ("cond_sub_uncond", "denoised_sub_uncond", "uncond_sub_cond", "denoised", "cond", "uncond", "model_input")
+BLEND_SCALE_MODES = ("none", "reverse_sampling", "sampling", "reverse_enabled_range", "enabled_range", "sampling_sin", "enabled_range_sin")
+
+
+def get_blend_scaling(*, model_sampling, scale_mode: str, sigma: float, sigma_t_max: torch.Tensor, start_sigma: float, end_sigma: float,
+                      offset: float, min_pct: float, max_pct: float) -> float:
+    """py/nodes/latent_operations.py:120-155: the factor on blend_strength.  Host arithmetic throughout."""
+    if scale_mode == "none":
+        return 1.0
+    if scale_mode in {"sampling", "sampling_sin", "reverse_sampling"}:
+        rev_sampling_pct = (model_sampling.timestep(sigma_t_max) / 999).clamp(0, 1).detach().item()
+        result = 1.0 - rev_sampling_pct if scale_mode == "sampling" else rev_sampling_pct
+    elif scale_mode in {"enabled_range", "enabled_range_sin", "reverse_enabled_range"}:
+        rev_range_pct = (sigma - end_sigma) / (start_sigma - end_sigma)
+        result = 1.0 - rev_range_pct if scale_mode == "enabled_range" else rev_range_pct
+    else:
+        raise ValueError("Bad blend_scale_mode")
+    if scale_mode.endswith("_sin"):
+        result = math.sin(result * math.pi)
+    return max(min_pct, min(result + offset, max_pct))
+
+
+class LatentOperationCFG:
+    """py/nodes/latent_operations.py:197-300: the function the node installs as a pre-CFG or post-CFG hook (and calls from its UNet wrapper
+    for ``model_input``).  Per call: one value read from the device (the largest sigma, as in the reference), ``hip_lib.cfg_op_prepare``,
+    the operations on fp32 tensors, ``hip_lib.cfg_op_finish``.  Inputs are never written; float32 / float16 / bfloat16 predictions go to the
+    kernels as they are and the result has the dtype of the tensor it replaces.
+
+    The reference keeps ``mode`` in a closure variable that the fallback of the ``*_sub_uncond`` modes rewrites, and its uncond gate reads
+    that variable BEFORE the call's own rewrite -- so the gate sees the mode the previous enabled call ended with.  ``self.mode`` is that
+    variable; reproduced as it is."""
+
+    NEEDS_UNCOND = frozenset({"uncond", "uncond_sub_cond", "denoised_sub_uncond"})
+
+    def __init__(self, *, model_sampling, operations: Sequence, mode: str, pred_flip_mode: bool, require_uncond: bool, start_sigma: float,
+                 end_sigma: float, blend_mode: str, blend_strength: float, blend_scale_mode: str, blend_scale_offset: float,
+                 blend_scale_min: float, blend_scale_max: float, immediate_blend: bool, blend_scaling=get_blend_scaling):
+        if blend_mode not in hip_lib.BLEND_IDS:
+            raise KeyError(blend_mode)
+        self.operations = tuple(operations)
+        self.blend_scaling = blend_scaling  # the node hands in its own static method (the reference calls cls.get_blend_scaling)
+        self.orig_mode = self.mode = mode
+        self.post_cfg_mode = mode in {"denoised", "denoised_sub_uncond"}
+        self.pred_flip_mode, self.require_uncond, self.immediate_blend = pred_flip_mode, require_uncond, immediate_blend
+        self.blend_mode, self.blend_strength = blend_mode, blend_strength
+        self.blend_scale_offset, self.blend_scale_min, self.blend_scale_max = blend_scale_offset, blend_scale_min, blend_scale_max
+        sigma_max, sigma_min = model_sampling.sigma_max.detach().item(), model_sampling.sigma_min.detach().item()
+        if start_sigma < 0:
+            start_sigma = sigma_max
+        start_sigma = max(sigma_min, min(sigma_max, start_sigma))
+        end_sigma = max(sigma_min, min(sigma_max, end_sigma))
+        if end_sigma > start_sigma:
+            start_sigma, end_sigma = end_sigma, start_sigma
+        if start_sigma == end_sigma:
+            blend_scale_mode = "none"
+        self.sigma_max, self.sigma_min = sigma_max, sigma_min
+        self.start_sigma, self.end_sigma, self.blend_scale_mode = start_sigma, end_sigma, blend_scale_mode
+
+    @staticmethod
+    def _operand(t: torch.Tensor, dtype=None) -> torch.Tensor:
+        if dtype is not None and t.dtype != dtype:
+            t = t.to(dtype)
+        return t if t.is_contiguous() else t.contiguous()
+
+    def __call__(self, args: dict):
+        x = args["input"]
+        cond_scale = args.get("cond_scale")
+        sigma_t = args["sigma"]
+        sigma = sigma_t.detach().max().item()  # the call's one read from the device
+        enabled = self.end_sigma <= sigma <= self.start_sigma
+        conds_out = args.get("conds_out", ())
+        post_cfg_mode = self.post_cfg_mode
+        uncond = args.get("uncond_denoised") if post_cfg_mode else (conds_out[1] if len(conds_out) > 1 else None)
+        if uncond is None and (self.require_uncond or self.mode in self.NEEDS_UNCOND):
+            enabled = False
+        if not enabled:
+            if self.mode == "model_input":
+                return x
+            return args["denoised"] if post_cfg_mode else conds_out
+        cond = conds_out[0] if not post_cfg_mode and len(conds_out) else None
+        if uncond is None and self.mode.endswith("_sub_uncond"):
+            self.mode = self.orig_mode.split("_", 1)[0]
+        else:
+            self.mode = self.orig_mode
+        mode = self.mode
+        if mode == "model_input":
+            t1, t2 = x, None
+        elif mode in {"cond", "cond_sub_uncond"}:
+            t1, t2 = cond, (uncond if mode == "cond_sub_uncond" else None)
+        elif mode in {"uncond", "uncond_sub_cond"}:
+            t1, t2 = uncond, (cond if mode == "uncond_sub_cond" else None)
+        else:
+            t1, t2 = args["denoised"], (uncond if mode == "denoised_sub_uncond" else None)
+        clamped = max(self.sigma_min, min(sigma, self.sigma_max))
+        curr_blend = self.blend_strength * self.blend_scaling(
+            scale_mode=self.blend_scale_mode, offset=self.blend_scale_offset, min_pct=self.blend_scale_min, max_pct=self.blend_scale_max,
+            model_sampling=args["model"].model_sampling, start_sigma=self.start_sigma, end_sigma=self.end_sigma, sigma=clamped,
+            # a host tensor of the value already read: timestep() then never waits for the device, wherever the model keeps its tables
+            sigma_t_max=torch.tensor(clamped, dtype=sigma_t.dtype if sigma_t.dtype.is_floating_point else torch.float32))
+        t1_orig = self._operand(t1)
+        dtype = t1_orig.dtype
+        t2c = None if t2 is None else self._operand(t2, dtype)
+        xc = sig = None
+        if self.pred_flip_mode:
+            xc = self._operand(x, dtype)
+            sig = sigma_t.detach().reshape(-1).to(device=t1_orig.device, dtype=torch.float32).contiguous()
+        result, t2f = hip_lib.cfg_op_prepare(xc, t1_orig, t2c, sig)  # result is the patch's own buffer, t2 or not
+        for operation in self.operations:
+            curr_result = utils.as_f32(operation(result, sigma=sigma, t2=t2f, cond=cond, uncond=uncond, cond_scale=cond_scale, raw_args=args))
+            result = hip_lib.blend(self.blend_mode, result, curr_result, curr_blend) if self.immediate_blend else curr_result
+        result = hip_lib.cfg_op_finish(result, t2f, xc, sig, t1_orig, None if self.immediate_blend else self.blend_mode, curr_blend)
+        if post_cfg_mode or mode == "model_input":
+            return result
+        conds_out = conds_out.copy()
+        conds_out[0 if mode.startswith("cond") else 1] = result
+        return conds_out

@@ -296,6 +296,29 @@ int sonar_minmax_rows_f32(const float* x, int64_t rows, int64_t inner, float* ou
 int sonar_minmax_rescale_f32(const float* x, int64_t rows, int64_t inner, const float* lo, const float* hi, float eps,
                              double target_min, double target_max, float* out, void* stream);
 
+/* ---------------------------------------------------------------- latent operations under CFG */
+/* SonarApplyLatentOperationCFG (py/nodes/latent_operations.py:246-300): the arithmetic on either side of the latent operations, one launch
+ * each.  x, t1, t2, t1_orig and out are n contiguous values of `dtype` (SONAR_DTYPE_*: widened to fp32 at load, `out` rounded once, to
+ * nearest even); result, t2_out / t2 and sigma are fp32.  sigma (device, nullable): NULL = no prediction flip, else sigma_n = 1 value or one
+ * per sample of `inner` consecutive elements (sigma_n = n / inner; inner must divide n and need not be a multiple of the vector width).
+ * Every operation is rounded on its own, in the reference's order, and the division is a true division.
+ *  sonar_cfg_op_prepare  f(t) = (x - t) / sigma[i / inner] with a flip, f(t) = t without;  t2_out = f(t2) (t2, t2_out nullable together);
+ *                        result = f(t1) - f(t2), or f(t1) without t2.  x may be NULL without a flip.
+ *  sonar_cfg_op_finish   r = result + t2 (t2 nullable: the buffer prepare wrote);  with a flip r = x - sigma[i / inner] * r;
+ *                        out = blend(t1_orig, r, w) (SONAR_BLEND_*, evaluated as sonar_blend_f32 does) or out = r for SONAR_CFG_BLEND_NONE
+ *                        (t1_orig may then be NULL).  out must not overlap an input.
+ * 16-byte aligned buffers take 4 elements per lane and access; any other alignment takes the one-element route.
+ * SONAR_ERR_ARG: n < 0, inner <= 0 or not a divisor of n, sigma_n neither 1 nor n / inner, an unknown dtype or blend mode, and for n > 0 a
+ * required pointer NULL.  n == 0 launches nothing (and asks for no buffer: an empty tensor has none). */
+#define SONAR_DTYPE_F32 0
+#define SONAR_DTYPE_F16 1
+#define SONAR_DTYPE_BF16 2
+#define SONAR_CFG_BLEND_NONE (-1)
+int sonar_cfg_op_prepare(int dtype, const void* x, const void* t1, const void* t2, const float* sigma, int64_t sigma_n, float* result,
+                         float* t2_out, int64_t n, int64_t inner, void* stream);
+int sonar_cfg_op_finish(int dtype, const float* result, const float* t2, const void* x, const float* sigma, int64_t sigma_n,
+                        const void* t1_orig, int blend_mode, float w, void* out, int64_t n, int64_t inner, void* stream);
+
 /* A pending global normalisation of a noise tensor (py/utils.py:100-105): the decision scale_noise(normalized=True) would take,
  * computed ON THE DEVICE from the tensor's (sum, sumsq) partials and left in device memory, so that the kernel that consumes the
  * noise (the sampler-step kernels below take it as `noise_norm`, nullable) applies `((v - mean) / std) * factor` -- only the parts
