@@ -152,9 +152,6 @@ constexpr int kTileElems = kTileIters * 256;
 // of the library starts with it: nothing for one line of arguments, one early batch of scalar loads otherwise.
 template <size_t BYTES>
 __device__ __forceinline__ void kernarg_touch() {
-#ifdef SONAR_NO_KERNARG_TOUCH  // (profiling builds: the A/B of this line)
-    return;
-#endif
     if constexpr (BYTES <= 64) return;  // one line: the kernel's own first load is the touch
     const uint32_t __attribute__((address_space(4)))* ka = (const uint32_t __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
     uint32_t any = 0;

@@ -41,17 +41,11 @@ struct BandsArgs {
     TapsSmall<T> dec, rec;
 };
 
-#ifndef SONAR_BANDS_STAGE_AHEAD
-#define SONAR_BANDS_STAGE_AHEAD 4  // values per thread of the last stage's NEXT tile requested a tile ahead (0: a tile's loads at its own start)
-#endif
-#ifndef SONAR_BANDS_STAGE_AHEAD_ONE
-#define SONAR_BANDS_STAGE_AHEAD_ONE 6  // ... when the stage reads ONE tensor in fp32 arithmetic (the two launches of a cond / uncond rule): 6 values 187 us per rule,
-                                       // 4 values 194; with two tensors staged (difference rules) 4 values 170 us, 6 values 177; in fp64 arithmetic (the tile route's
-                                       // deeper-levels call is this form) 6 values cost 12-29 us per rule (same-box sweeps, round 5)
-#endif
-#ifndef SONAR_BANDS_ROWS_AHEAD
-#define SONAR_BANDS_ROWS_AHEAD 1  // level 1 down: the next item's rows requested an item ahead (0: every item waits for its own loads)
-#endif
+constexpr int kStageAhead = 4;  // values per thread of the last stage's NEXT tile requested a tile ahead
+// ... when the stage reads ONE tensor in fp32 arithmetic (the two launches of a cond / uncond rule).  Measured (same-box sweeps, round 5):
+// 6 values 187 us per rule, 4 values 194; with two tensors staged (difference rules) 4 values 170 us, 6 values 177; in fp64 arithmetic
+// (the tile route's deeper-levels call is this form) 6 values cost 12-29 us per rule
+constexpr int kStageAheadOne = 6;
 #ifdef SONAR_BANDS_TRACE  // profiling builds (scratch/bands_trace.py): thread 0's cycle stamps of the first plane of every workgroup
 __device__ unsigned long long g_bands_trace[512 * 32];
 #define SONAR_BANDS_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 512 && p == (int64_t)blockIdx.x) g_bands_trace[blockIdx.x * 32 + (slot)] = __builtin_readcyclecounter(); } while (0)
@@ -335,8 +329,8 @@ __global__ void __launch_bounds__(NT) wcfg_bands_kernel(const TIO* __restrict__ 
             // (`scratch/bands_trace.py`: this stage is 46 % of a plane's time in the single-launch kernel, 42 % in the deeper levels' call).
             // The request is unconditional (the last tile asks for itself again, from L2): under a condition the loaded registers would
             // merge with their old values in a copy that waits for the loads on the spot (see spectral_filter128_kernel).
-            constexpr int KP = (!HASB && sizeof(T) == 4) ? SONAR_BANDS_STAGE_AHEAD_ONE : SONAR_BANDS_STAGE_AHEAD;
-            [[maybe_unused]] St pre[KP > 0 ? KP : 1];
+            constexpr int KP = (!HASB && sizeof(T) == 4) ? kStageAheadOne : kStageAhead;
+            St pre[KP];
             // (Measured and dropped, twice: the x pairs the tail subtracts from, requested a tile ahead -- selected by item number inside the
             // tail's loop they keep 70 more registers alive and a CU holds one workgroup instead of two: 198 -> 310 us -- or a phase ahead
             // with the first two items peeled off the loop: 30-40 more registers, 171 -> 240 us.)
@@ -349,17 +343,15 @@ __global__ void __launch_bounds__(NT) wcfg_bands_kernel(const TIO* __restrict__ 
                     else pre[k] = St{pa[at]};
                 }
             };
-            if constexpr (KP > 0) request(0);
+            request(0);
             SONAR_BANDS_LAP_BEGIN();
             for (int y0 = 0; y0 < H; y0 += a.rows_out) {
                 const int tz = tap_zero<T, FT>();
                 const int th = min(a.rows_out, H - y0);
-                if constexpr (KP > 0) {
 #pragma unroll
-                    for (int k = 0; k < KP; ++k) {
-                        const int it = tid + k * NT;
-                        if (it < th * W) cu[it] = pre[k];
-                    }
+                for (int k = 0; k < KP; ++k) {
+                    const int it = tid + k * NT;
+                    if (it < th * W) cu[it] = pre[k];
                 }
                 for (int it = tid + KP * NT; it < th * W; it += NT) {
                     const int at = y0 * W + it;
@@ -368,7 +360,7 @@ __global__ void __launch_bounds__(NT) wcfg_bands_kernel(const TIO* __restrict__ 
                 }
                 __syncthreads();
                 SONAR_BANDS_LAP(20);
-                if constexpr (KP > 0) request(y0 + a.rows_out < H ? y0 + a.rows_out : y0);
+                request(y0 + a.rows_out < H ? y0 + a.rows_out : y0);
                 for (WalkN<NT> wk(tid, w1); 2 * wk.r < th; wk.next(w1)) {
                     const int mp = wk.r, xo = wk.c, m = (y0 >> 1) + mp;
                     T e, o, e2 = T(0), o2 = T(0);
@@ -480,11 +472,6 @@ static bool bands_plan(BandsArgs<T>& a, size_t& lds_bytes, int64_t H, int64_t W,
         return (size_t)a.off_maps + (size_t)ints * sizeof(int);
     };
     auto per_cu = [](size_t bytes) { return (160 * 1024) / (bytes + 512); };
-    static const int forced_rows = [] { const char* e = getenv("SONAR_BANDS_ROWS_OUT"); return e ? atoi(e) : 0; }();  // (experiments)
-    if (forced_rows > 0) {
-        lds_bytes = layout(forced_rows);
-        return lds_bytes <= budget;
-    }
     // Output rows per tile of the last stage.  First what LDS allows: shorter tiles when they buy another resident workgroup.  Then, among
     // the heights that keep that many workgroups resident, the one whose item counts waste the fewest rounds of the workgroup's threads
     // (round 5): the stage's second phase has (rows / 2) x W1 items, its third rows x ceil(W / 2), each a dependent chain of LDS reads
@@ -495,8 +482,7 @@ static bool bands_plan(BandsArgs<T>& a, size_t& lds_bytes, int64_t H, int64_t W,
         for (int r : {kLowRows / 2, kLowRows}) want_cu = std::max(want_cu, (size_t)per_cu(layout(r, lean != 0)));
     // ... and what the registers allow: the 512-thread instantiations take 67-77 of them (six or seven waves per SIMD: three workgroups);
     // a plan for four pays for them with short tiles and gets three (fp64 deeper levels: 231 against 217 us on the difference rule)
-    static const int cap_cu = [] { const char* e = getenv("SONAR_BANDS_WANT_CU"); return e ? atoi(e) : 3; }();  // (the variable: experiments)
-    if (cap_cu > 0) want_cu = std::min(want_cu, (size_t)cap_cu);
+    want_cu = std::min<size_t>(want_cu, 3);
     const int nt = sizeof(T) == 8 && io_size == 4 && want_cu <= 1 ? 1024 : 512;  // (wcfg_bands: whole latent planes in fp64 take 1024 threads)
     int best_rows = kLowRows / 2;
     bool best_lean = true;
@@ -517,15 +503,11 @@ static bool bands_plan(BandsArgs<T>& a, size_t& lds_bytes, int64_t H, int64_t W,
     }
     if (best_cost > 1e29) return false;
     lds_bytes = layout(best_rows, best_lean);
-    static const bool plan_debug = getenv("SONAR_BANDS_PLAN_DEBUG") != nullptr;  // (experiments)
-    if (plan_debug)
-        fprintf(stderr, "bands_plan %dx%d T%zu io%zu v%zu hasb%d: rows_out %d lean %d cost %.1f lds %zu per_cu %zu want %zu rows1 %d rows_up %d %d %d\n", (int)H, (int)W,
-                sizeof(T), io_size, v_size, (int)hasb, best_rows, (int)best_lean, best_cost, lds_bytes, (size_t)per_cu(lds_bytes), want_cu, a.rows1, a.rows_up[2],
-                a.rows_up[3], a.rows_up[4]);
     return lds_bytes <= budget;
 }
 
-constexpr bool bands_rows_ahead_ok(size_t io_size, int ft) { return SONAR_BANDS_ROWS_AHEAD && io_size == 4 && ft <= 10; }  // (12 taps spill at the 1024-thread instantiation's 128 registers)
+// level 1 down: the next item's rows are requested an item ahead
+constexpr bool bands_rows_ahead_ok(size_t io_size, int ft) { return io_size == 4 && ft <= 10; }  // (12 taps spill at the 1024-thread instantiation's 128 registers)
 // what the plan assumed about the kernel's two LDS-halving parameters: the cV planes in fp32 (fp64 arithmetic, coefficient-plane I/O: the
 // tile route's deeper levels, when the process keeps detail bands in fp32), single staged values (no second tensor; coefficient-plane or
 // fp32 I/O -- the fp64 latent kernel holds one workgroup per CU either way and keeps the pair form)

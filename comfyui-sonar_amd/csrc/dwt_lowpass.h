@@ -12,17 +12,13 @@
 // high_precision_mode default) or fp32 arithmetic; results agree with the band-by-band path to rounding (tests compare both with
 // the reference-run fixtures).
 #pragma once
-#ifndef SONAR_LOWPASS_NT
-#define SONAR_LOWPASS_NT 0  // profiling builds: the output phase's 16-byte stores with the non-temporal hint
-#endif
 #include "dwt_tile.h"
 
 namespace sonar {
 
-#ifndef SONAR_LOW_THREADS
-#define SONAR_LOW_THREADS 512  // (A/B, round 6: 768 / 1024 threads per plane are SLOWER -- 122.9 / 116.2 us against 95.5 fp64, profiles/r06_experiments.md)
-#endif
-constexpr int kLowThreads = SONAR_LOW_THREADS;   // 8 waves per plane: more than the 4 of round 2 hide more of the phases' latency; beyond 8 the phases' fixed cost wins
+// 8 waves per plane: more than the 4 of round 2 hide more of the phases' latency; beyond 8 the phases' fixed cost wins (measured, round 6:
+// 768 / 1024 threads per plane were SLOWER -- 122.9 / 116.2 us against 95.5 fp64, profiles/r06_experiments.md)
+constexpr int kLowThreads = 512;
 constexpr int kLowRows = 16;       // output rows per level-1 analysis tile / final synthesis tile
 constexpr int kLowMaxLevels = 8;
 
@@ -108,7 +104,7 @@ __device__ __forceinline__ void synth_low_pair(int m, int n, int mode, const T* 
 // ZERO: zero padding on the way down -- the only extension whose tables hold "no source" entries; the other modes' taps carry no clamp
 // and no select
 template <typename T, int FT, bool ZERO>
-__global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg_lowpass_kernel(const float* __restrict__ cond, const float* __restrict__ uncond,
+__global__ void __launch_bounds__(kLowThreads, 1) wcfg_lowpass_kernel(const float* __restrict__ cond, const float* __restrict__ uncond,
                                                                     const float* __restrict__ xin, float* __restrict__ out, LowArgs<T> a) {
     kernarg_touch_for(cond, uncond, xin, out, a);
     auto at0 = [](int s) { return ZERO ? max(s, 0) : s; };
@@ -131,9 +127,6 @@ __global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg
             maps[a.map_w[j] + i] = (j == 1 && sx >= 0) ? (sx & 1) * ((Wp + 1) >> 1) + (sx >> 1) : sx;
         }
     }
-#ifdef SONAR_LOW_STAGGER  // profiling builds: the k-th resident workgroup of a CU starts k * SONAR_LOW_STAGGER (x 0.85 us) late
-    for (int i = 0; i < (int)(blockIdx.x / 256) * SONAR_LOW_STAGGER; ++i) __builtin_amdgcn_s_sleep(32);
-#endif
     const int H = a.H[0], W = a.W[0], h1 = a.H[1], w1 = a.W[1];
     const int Wh = (W + 1) >> 1, Ws = 2 * Wh;  // parity-split row of the level-1 scratch: slot(x) = (x & 1) Wh + x / 2
     for (int64_t p = blockIdx.x; p < a.planes; p += gridDim.x) {
@@ -147,9 +140,6 @@ __global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg
             const int* const xmap = maps + a.map_w[1];
             constexpr int THS = 4, NRS = 2 * THS + FT - 2;
             T* const tmp1 = lds + a.off_tmp1;
-#ifdef SONAR_LOW_NOANALYSIS
-            if (false)
-#endif
             for (int y0 = 0; y0 < h1; y0 += a.rows1) {
                 const int th = min(a.rows1, h1 - y0);
                 // along H: one thread per (row group of 4, column); each input row of the group's window is read once.  (Two columns per
@@ -196,9 +186,6 @@ __global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg
             }
         }
         // ---------------------------------------------------------------- deeper levels: LL_j from LL_{j-1}, all in LDS
-#ifdef SONAR_LOW_NODEEP
-        if (false)
-#endif
         for (int j = 2; j <= J; ++j) {
             const int Hp = a.H[j - 1], Wp = a.W[j - 1], h = a.H[j], w = a.W[j];
             const T* const src = lds + a.off_ll[j - 1];
@@ -240,9 +227,6 @@ __global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg
             for (int it = tid; it < a.H[J] * a.W[J]; it += kLowThreads) top[it] *= gJ;
             __syncthreads();
         }
-#ifdef SONAR_LOW_NODEEP
-        if (false)
-#endif
         for (int j = J; j >= 2; --j) {
             const int h = a.H[j], w = a.W[j], Ho = a.H[j - 1], Wo = a.W[j - 1];  // only the rows / columns the level below keeps
             const T* const B = lds + a.off_ll[j];
@@ -295,11 +279,7 @@ __global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg
                         const int yl = wk.r, m = 2 * wk.c;
                         const T* row = tmp + yl * w1;
                         const uint32_t at = (uint32_t)((y0 + yl) * W + 4 * wk.c);
-#ifdef SONAR_LOW_NOREREAD  // profiling builds: what the second read of cond / uncond costs
-                        float4 c4 = make_float4(1.0f, 1.0f, 1.0f, 1.0f), u4 = make_float4(2.0f, 2.0f, 2.0f, 2.0f);
-#else
                         float4 c4 = at_u32<float4>(pc, at), u4 = at_u32<float4>(pu, at);
-#endif
                         float4 x4 = px ? at_u32<float4>(px, at) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                         T cf[K + 1];  // coefficients m .. m + K (clamped as synth_low_pair clamps: beyond the valid length only)
 #pragma unroll
@@ -318,7 +298,7 @@ __global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg
                         const T r3 = fma_t(a.ku, (T)u4.w, a.kt * fma_t(g0, (T)c4.w - (T)u4.w, o1));
                         float4 res = make_float4((float)r0, (float)r1, (float)r2, (float)r3);
                         if (px) res = make_float4(x4.x - res.x, x4.y - res.y, x4.z - res.z, x4.w - res.w);
-                        store4<(SONAR_LOWPASS_NT != 0)>(&at_u32<float>(po, at), res.x, res.y, res.z, res.w);
+                        store4<false>(&at_u32<float>(po, at), res.x, res.y, res.z, res.w);
                     }
                 } else
                 for (Walk2 wk(tid, wp); wk.r < th; wk.next(wp)) {
@@ -332,13 +312,8 @@ __global__ void __launch_bounds__(kLowThreads, (kLowThreads > 512 ? 8 : 1)) wcfg
                     // item ahead measured the same for fp32 and slower for fp64)
                     float2 c2 = make_float2(0.0f, 0.0f), u2 = c2, x2 = c2;
                     if (vec) {
-#ifdef SONAR_LOW_NOREREAD  // profiling builds: what the second read of cond / uncond costs
-                        c2 = make_float2(1.0f, 1.0f);
-                        u2 = make_float2(2.0f, 2.0f);
-#else
                         c2 = *reinterpret_cast<const float2*>(pc + at);
                         u2 = *reinterpret_cast<const float2*>(pu + at);
-#endif
                         if (px) x2 = *reinterpret_cast<const float2*>(px + at);
                     }
                     T e, o;
@@ -402,22 +377,17 @@ static bool lowpass_plan(LowArgs<T>& a, size_t& lds_bytes, int64_t H, int64_t W,
     // ... and of the heights the scratch holds, the one whose phases waste the fewest rounds of the workgroup's threads (round 5, as in
     // dwt_bands.h's plan): the synthesis along H has (rows / 2) x W1 items, the pass along W rows x W / 4 -- 36 rows of a 128 x 128 plane
     // (db4) are 1206 and 1152 items for 512 threads, three rounds each; 30 rows are two (fp32 85.3 -> 83.3 us, fp64 92.5 -> 89.7 us)
-    static const int forced_rows = [] { const char* e = getenv("SONAR_LOW_ROWS_OUT"); return e ? atoi(e) : 0; }();  // (experiments: at most the scratch's)
-    if (forced_rows > 0) {
-        a.rows_out = std::min(a.rows_out, std::max(2, forced_rows / 2 * 2));
-    } else {
-        int best = a.rows_out;
-        long best_cost = -1;
-        for (int r = a.rows_out; r >= kLowRows; r -= 2) {
-            const long tiles = ((int)H + r - 1) / r, items2 = (long)(r / 2) * a.W[1], items3 = (long)r * (((int)W + 3) / 4);
-            const long cost = tiles * ((items2 + kLowThreads - 1) / kLowThreads + (items3 + kLowThreads - 1) / kLowThreads + 1);
-            if (best_cost < 0 || cost < best_cost) {
-                best_cost = cost;
-                best = r;
-            }
+    int best = a.rows_out;
+    long best_cost = -1;
+    for (int r = a.rows_out; r >= kLowRows; r -= 2) {
+        const long tiles = ((int)H + r - 1) / r, items2 = (long)(r / 2) * a.W[1], items3 = (long)r * (((int)W + 3) / 4);
+        const long cost = tiles * ((items2 + kLowThreads - 1) / kLowThreads + (items3 + kLowThreads - 1) / kLowThreads + 1);
+        if (best_cost < 0 || cost < best_cost) {
+            best_cost = cost;
+            best = r;
         }
-        a.rows_out = best;
     }
+    a.rows_out = best;
     a.off_maps = (int)(((size_t)at * sizeof(T) + 15) / 16 * 16);
     lds_bytes = (size_t)a.off_maps + (size_t)ints * sizeof(int);
     return lds_bytes <= 80 * 1024;  // two workgroups per CU

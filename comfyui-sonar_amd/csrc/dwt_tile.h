@@ -21,13 +21,10 @@ namespace sonar {
 // argument's tap arrays behind an opaque zero, made per stage, keeps the loads inside it (they hit the scalar cache; used by the band kernel,
 // dwt_bands.h -- in the tile kernels below the lane moves are not the taps: no change there).  Up to 14
 // taps: beyond, the compiler answers the run-time index with a private copy of the argument block (scratch: never).
-#ifndef SONAR_TAPS_LOCAL
-#define SONAR_TAPS_LOCAL 1
-#endif
 template <typename T, int FT>
 __device__ __forceinline__ int tap_zero() {
     int z = 0;
-    if constexpr (sizeof(T) == 8 && FT <= 14 && SONAR_TAPS_LOCAL) asm volatile("" : "+s"(z));
+    if constexpr (sizeof(T) == 8 && FT <= 14) asm volatile("" : "+s"(z));
     return z;
 }
 template <typename T>

@@ -25,10 +25,7 @@ __device__ __forceinline__ Pack<V> load(const float* p, int64_t i) {
     }
     return r;
 }
-#ifndef SONAR_EW_NT
-#define SONAR_EW_NT 0  // profiling builds: every elementwise kernel's 16-byte stores with the non-temporal hint
-#endif
-template <int V, bool NT = (SONAR_EW_NT != 0)>
+template <int V, bool NT = false>  // (NT: the 16-byte stores with the non-temporal hint)
 __device__ __forceinline__ void store(float* p, int64_t i, const Pack<V>& r) {
     if constexpr (V == 4) {
         store4<NT>(p + i, r.v[0], r.v[1], r.v[2], r.v[3]);

@@ -1238,33 +1238,14 @@ constexpr size_t kPyramidLdsBudget = 64 * 1024;
 // The grids and the stretched rows of a plane take up to 64 KB of LDS, so two workgroups fit a CU: with 256 threads that is two
 // waves per SIMD (one at batch 64, where there is a plane per CU) and the tile loop runs at the latency of its dependent chains.
 // kPyrParts 256-thread parts share one plane's LDS instead.
-#ifndef SONAR_PYR_PARTS
-#define SONAR_PYR_PARTS 2
-#endif
-constexpr int kPyrParts = SONAR_PYR_PARTS;
-#ifndef SONAR_PYR_STRETCH
-#define SONAR_PYR_STRETCH 1
-#endif
+constexpr int kPyrParts = 2;
 // items a thread stretches along x per round (XROWS).  Re-swept once the column-fixed path had made an item cheap (same box, batch 512 / 64,
 // normalised call): 8 items 92.1 / 22.3 us, 4 items (the setting while an item was a table read and two dependent gathers) 89.7 / 21.9, 3 items
 // 88.6 / 22.0, 2 items 88.5 / 21.7, **1 item 87.3 / 21.6**
-constexpr int kPyrStretch = SONAR_PYR_STRETCH;
-#ifndef SONAR_PYR_GROUP
-#define SONAR_PYR_GROUP 1
-#endif
-#ifndef SONAR_PYR_GROUP_PRE
-#define SONAR_PYR_GROUP_PRE 1
-#endif
-constexpr int kPyrGroup = SONAR_PYR_GROUP, kPyrGroupPre = SONAR_PYR_GROUP_PRE;  // burst steps whose level reads are in flight together (XROWS)
+constexpr int kPyrStretch = 1;
+constexpr int kPyrGroup = 1, kPyrGroupPre = 1;  // burst steps whose level reads are in flight together (XROWS)
 constexpr int kPyrBlock = kPyrParts * kBlock;
 static_assert((kPyrParts & (kPyrParts - 1)) == 0 && kTileIters % kPyrParts == 0, "parts split a tile's burst evenly");
-#ifndef SONAR_PYR_UNROLL_N
-#define SONAR_PYR_UNROLL_N 1
-#endif
-#define SONAR_PYR_PRAGMA(x) _Pragma(#x)
-#define SONAR_PYR_UNROLL_(n) SONAR_PYR_PRAGMA(unroll n)
-#define SONAR_PYR_UNROLL_X(n) SONAR_PYR_UNROLL_(n)
-#define SONAR_PYR_UNROLL SONAR_PYR_UNROLL_X(SONAR_PYR_UNROLL_N)
 
 // fold (nullable y): the values are folded into a chain's running sum, out == fold.y (sonar_pyramid_generate_acc_f32); PRE != 0: the
 // chain's previous item rides along (Prefix above) -- its generator shares this kernel's tile keying, so its state simply walks the
@@ -1568,9 +1549,6 @@ __device__ __forceinline__ void pyramid_plane_body(float* out, int64_t planes, i
         // the shared tile too and each keeps its own part)
         const int64_t g0 = elem_offset + p * (int64_t)HW;
         const int64_t tile_first = g0 / kTileElems, tile_last = (g0 + HW - 1) / kTileElems;
-#ifdef SONAR_PYR_SETUP_ONLY  // profiling builds: what the per-plane setup (grids, tables, stretched rows) costs
-        if (oplane != nullptr) continue;
-#endif
         // a tile's burst is split between the parts: part k runs iterations [k, k + 1) * kTileIters / kPyrParts after stepping its
         // generators over the iterations before them (8 plain instructions per word instead of a Box-Muller pair)
         for (int64_t t = tile_first + wave % (kBlock / 64); t <= tile_last; t += kBlock / 64) {
@@ -1706,7 +1684,7 @@ __device__ __forceinline__ void pyramid_plane_body(float* out, int64_t planes, i
                 else run(pdiv);
                 continue;
             }
-SONAR_PYR_UNROLL
+#pragma unroll 1
             for (int it = 0; it < kIters; ++it, e += 256, y += dy, x4 += dx, y += x4 >= W, x4 -= x4 >= W ? W : 0) {
                 float v[4];
                 rng.normal4(v);
@@ -1823,8 +1801,7 @@ static bool launch_pyramid_plane(float* out, int64_t planes, int64_t H, int64_t 
     const size_t lds_x = lds + rows * W * sizeof(float);
     if (W % 4 != 0 || elem_offset % (H * W) != 0 || lds > kPyramidLdsBudget) return false;
     const bool xrows = mode == 0 && W % 4 == 0 && lds_x <= kPyramidLdsBudget;
-    static const int grid_cap = [] { const char* e = getenv("SONAR_PYR_GRID"); return e ? atoi(e) : kNPart; }();
-    const int g = (int)std::min<int64_t>(planes, std::min(grid_cap, kNPart));
+    const int g = (int)std::min<int64_t>(planes, kNPart);
     if (slots) *slots = g;
     const bool nt = nt_stores_host(planes * H * W);
 #define SONAR_PPN(ST, XR, P, N) \
@@ -1871,8 +1848,7 @@ static bool launch_pyramid_ahead(float* out, int64_t planes, int64_t H, int64_t 
     int gf_now = 0, gf_next = 0;
     const size_t lds_now = now ? pyramid_xrows_lds(*now, H, W, &gf_now) : 1, lds_next = pyramid_xrows_lds(next, H, W, &gf_next);
     if (W % 4 != 0 || elem_offset % (H * W) != 0 || !lds_now || !lds_next) return false;
-    static const int grid_cap = [] { const char* e = getenv("SONAR_PYR_GRID"); return e ? atoi(e) : kNPart; }();
-    const int g = (int)std::min<int64_t>(planes, std::min(grid_cap, kNPart));  // launch_pyramid_plane's grid: the partials' grouping
+    const int g = (int)std::min<int64_t>(planes, kNPart);  // launch_pyramid_plane's grid: the partials' grouping
     PyrAhead ah{};
     ah.na = na;
     ah.npart = npart;
@@ -2562,8 +2538,7 @@ extern "C" int sonar_perlin_noise_ahead_f32(const float* terms, float* out, int6
     a.tile_blocks = tile_grid(a.n, elem_offset);
     // a wave with a tile or more of its own to store has stores in flight to hide the next call's statistics behind (batch >= 256 SDXL
     // latents: the capped grid); below that the two passes go to separate blocks, twice as many waves with one short chain each
-    static const int fuse_env = [] { const char* e = getenv("SONAR_PERLIN_FUSED"); return e ? atoi(e) : -1; }();  // (A/B)
-    a.fused = terms_next && (fuse_env >= 0 ? fuse_env != 0 : a.tile_blocks == kNPart) ? 1 : 0;
+    a.fused = terms_next && a.tile_blocks == kNPart ? 1 : 0;
     hipLaunchKernelGGL(perlin_ahead_kernel, dim3(a.lat_blocks + a.tile_blocks * (terms_next && !a.fused ? 2 : 1)), dim3(kBlock), 0, st, a);
     return check_launch(what);
 }
@@ -2765,8 +2740,7 @@ extern "C" int sonar_pyramid_noise_ahead_f32(float* out, int64_t planes, int64_t
                   "%s: a level table is beyond the plane kernel's stretched-rows form (nothing was launched)", what);
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = planes * H * W;
-    static const int grid_cap = [] { const char* e = getenv("SONAR_PYR_GRID"); return e ? atoi(e) : kNPart; }();
-    const int slots = (int)std::min<int64_t>(planes, std::min(grid_cap, kNPart));
+    const int slots = (int)std::min<int64_t>(planes, kNPart);
     if (!have_stats) {
         // nobody left this call's statistics: its planes once without stores (the same partials the ordinary generating launch leaves)
         SONAR_REQUIRE(launch_pyramid_ahead(out, planes, H, W, nullptr, stream_id, now, stream_id, seed, elem_offset, NormArgs{}, 0, partials, st),

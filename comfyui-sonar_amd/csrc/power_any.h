@@ -68,9 +68,7 @@ static int launch_power_any(int what, const float* z, const float* filter, float
 // columns of one plane -- runs line_dft over them and writes the result; lengths up to kLinesMax, any factorisation (a factor the
 // codelets do not cover costs that pass its direct sums: 512 = 16 x 32 is sixteen terms per value, not 512).
 constexpr int kLinesThreads = 512;
-#ifndef SONAR_LINES_AHEAD
-#define SONAR_LINES_AHEAD 2  // lines_c2r_kernel<.., CR1 > 0>: chunks of 8 values per thread of the next batch requested a batch ahead (0: none)
-#endif
+constexpr int kLinesAhead = 2;  // lines_c2r_kernel<.., CR1 > 0>: chunks of 8 values per thread of the next batch requested a batch ahead
 constexpr int kLinesMax = 2048;
 constexpr size_t kLinesLds = 64 * 1024;  // two workgroups per CU
 
@@ -246,7 +244,7 @@ __global__ void __launch_bounds__(kLinesThreads, 4) lines_c2r_kernel(const c32* 
     // third of a batch's time behind its own loads (`scratch/lines_trace.py`: 8.5 k of 26 k ticks).  The run-time instantiation has no
     // registers to spare for it (it spilled 4-12 and lost what the request gained).  The loop is split at the request, not closed behind the
     // stores (see spectral_filter128_kernel).
-    constexpr int U = 8, PF = CR1 > 0 ? SONAR_LINES_AHEAD : 0;
+    constexpr int U = 8, PF = CR1 > 0 ? kLinesAhead : 0;
     [[maybe_unused]] c32 ahead[PF > 0 ? PF : 1][U];
     auto request = [&](int64_t r0) {
         const c32* __restrict__ src = y + r0 * S;

@@ -27,12 +27,6 @@ constexpr size_t kAnyLdsLimit = 160 * 1024 - 2048;
 // twiddles, A transforms of length B).  Every coefficient is a compile-time constant (static_for hands the loop indices to the
 // lambdas as types), so a codelet is straight-line packed arithmetic on register pairs.
 constexpr int kAnyCodelet = 16;
-#ifndef SONAR_ANY_STORE16
-#define SONAR_ANY_STORE16 1
-#endif
-#ifndef SONAR_ANY_PRIMES  // codelets for 17 and 19 too (136 = 8 x 17 and 152 = 8 x 19 are SDXL sides): 104 x 152 216 -> 152 us, the other sizes +3 %
-#define SONAR_ANY_PRIMES 1
-#endif
 
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -191,8 +185,9 @@ struct AnyPlan {
 // (+ 16: the pass-per-launch line kernels and the column-block kernel) are spill-free; the lengths 13 - 19 exist as COMPILE-TIME factors
 // only (power_buckets_*.hip), where a kernel holds exactly its four codelets.
 constexpr int kSetSmall = 0, kSetLines = 1, kSetAll = 2;
+// (codelets for 17 and 19 too -- 136 = 8 x 17 and 152 = 8 x 19 are SDXL sides; measured: 104 x 152 216 -> 152 us, the other sizes +3 %)
 constexpr bool radix_in_set(int n, int set) {
-    return n >= 2 && (n <= 12 || (set >= kSetLines && n == 16) || (set >= kSetAll && (n <= kAnyCodelet || (SONAR_ANY_PRIMES && (n == 17 || n == 19)))));
+    return n >= 2 && (n <= 12 || (set >= kSetLines && n == 16) || (set >= kSetAll && (n <= kAnyCodelet || (n == 17 || n == 19))));
 }
 static inline bool codelet_len(int n, int set) { return n == 1 || radix_in_set(n, set); }
 static inline void best_split(int n, int& n1, int& n2, int set) {
@@ -428,22 +423,13 @@ __device__ __forceinline__ void codelet_pass1(c32* A, int N1, int lines, int es,
 }
 
 #define SONAR_ANY_RADICES(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(19)
-// not inlined: four call sites per kernel, fifteen codelets per pass
-#ifndef SONAR_ANY_INLINE
-#define SONAR_ANY_INLINE 1
-#endif
-#if SONAR_ANY_INLINE
-#define SONAR_ANY_LINKAGE __forceinline__
-#else
-#define SONAR_ANY_LINKAGE __noinline__
-#endif
 // CR1 / CR2 > 0: the factor is known at compile time (the SDXL buckets' kernels, power_buckets_*.hip) -- the pass IS that codelet.  The
 // run-time switch over all seventeen codelets, force-inlined at four call sites, made the register allocator provide for the largest
 // of them everywhere: every instantiation spilled 32-74 vector registers at its 128 (round 4), and a kernel with a scratch segment costs
 // the process a 50-90 ms queue stall when the runtime sizes the scratch.
 // SET: the codelets of the run-time switch (radix_in_set); a length outside it runs as direct sums (line_dft_pass).
 template <int NT, bool FWD, int CR2 = 0, int SET = kSetSmall>
-__device__ SONAR_ANY_LINKAGE void line_pass1(c32* A, const c32* tw, int TN, int ts, int N1, int N2, int lines, int es, int ls, int tid) {
+__device__ __forceinline__ void line_pass1(c32* A, const c32* tw, int TN, int ts, int N1, int N2, int lines, int es, int ls, int tid) {
     if constexpr (CR2 == 1) {
         return;
     } else if constexpr (CR2 > 1) {
@@ -459,7 +445,7 @@ __device__ SONAR_ANY_LINKAGE void line_pass1(c32* A, const c32* tw, int TN, int 
     }
 }
 template <int NT, bool FWD, int CR1 = 0, int CR2 = 0, int SET = kSetSmall>
-__device__ SONAR_ANY_LINKAGE void line_dft(c32* A, const c32* tw, int TN, int ts, int N1, int N2, int lines, int es, int ls, int tid) {
+__device__ __forceinline__ void line_dft(c32* A, const c32* tw, int TN, int ts, int N1, int N2, int lines, int es, int ls, int tid) {
     if constexpr (CR1 > 0) {
         radix_pass0<NT, CR1, FWD>(A, tw, ts, N2, lines, es, ls, tid);
     } else {
@@ -560,12 +546,9 @@ __device__ __forceinline__ void c2r_pass0(c32* A, const c32* __restrict__ twW, i
 }
 
 // rows of the inverse: pre-twiddle + length-M complex inverse DFT (value m of a row is then (x[2m], x[2m+1]))
-#ifndef SONAR_ANY_FUSE_C2R
-#define SONAR_ANY_FUSE_C2R 1
-#endif
 template <int NT, int CR1 = 0, int CR2 = 0, int SET = kSetSmall>
-__device__ SONAR_ANY_LINKAGE void c2r_rows(c32* A, const c32* twW, int W, int N1, int N2, int H, int M, int S, int fuse, int tid) {
-    if (!SONAR_ANY_FUSE_C2R || !fuse) {  // uniform
+__device__ __forceinline__ void c2r_rows(c32* A, const c32* twW, int W, int N1, int N2, int H, int M, int S, int fuse, int tid) {
+    if (!fuse) {  // uniform
         c2r_pretwiddle<NT>(A, twW, H, M, S, tid);
         line_dft<NT, false, CR1, CR2, SET>(A, twW, W, 2, N1, N2, H, 1, S, tid);
         return;
@@ -734,7 +717,7 @@ __global__ void __launch_bounds__(NT, 4) power_irfft2_any_kernel(const float* __
             } else {
                 // ---- forward r2c: rows as W/2 complex values, forward DFT, split into the half-spectrum, forward columns, x filter
                 const float* xin = z + plane * (int64_t)H * W;
-                if (SONAR_ANY_STORE16 && (M & 1) == 0 && (reinterpret_cast<uintptr_t>(z) & 15u) == 0) {  // uniform: 16-byte loads, two values per item
+                if ((M & 1) == 0 && (reinterpret_cast<uintptr_t>(z) & 15u) == 0) {  // uniform: 16-byte loads, two values per item
                     const int Mh = M >> 1, hdr = NT / Mh, hdm = NT - hdr * Mh;
                     int hr = tid / Mh, hm = tid - hr * Mh;
                     for (int j = tid; j < H * Mh; j += NT) {
@@ -813,7 +796,7 @@ __global__ void __launch_bounds__(NT, 4) power_irfft2_any_kernel(const float* __
             SONAR_ANY_STAMP(4);
             float* const oplane = out + plane * (int64_t)H * W;
             float ps = 0.0f, pq = 0.0f;
-            if (SONAR_ANY_STORE16 && (M & 1) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {  // uniform
+            if ((M & 1) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {  // uniform
                 // two adjacent values of a row per item: 16-byte stores (the store phase is bound by its memory instructions)
                 const int Mh = M >> 1, hdr = NT / Mh, hdm = NT - hdr * Mh;
                 int hr = tid / Mh, hm = tid - hr * Mh;

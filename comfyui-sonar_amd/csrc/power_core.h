@@ -120,42 +120,15 @@ __device__ __forceinline__ c32 cmulc(c32 a, c32 b) {  // a * conj(b)
 
 constexpr int split_n1(int n) { return n >= 256 ? 16 : n >= 64 ? 8 : n == 32 ? 4 : n == 16 ? 2 : 1; }
 
-#ifndef SONAR_FILTER_IN_PASS
-#define SONAR_FILTER_IN_PASS 1  // FAST spectral filter: multiply by the filter in the inverse column pass a
-#endif
-#ifndef SONAR_ROW32_SPLIT8
-#define SONAR_ROW32_SPLIT8 1
-#endif
-#ifndef SONAR_FFT_THREADS
-#define SONAR_FFT_THREADS 512
-#endif
-#ifndef SONAR_FFT_WAVES
-#define SONAR_FFT_WAVES 4
-#endif
-#ifndef SONAR_FFT_UNROLL
-#define SONAR_FFT_UNROLL 1
-#endif
-#define SONAR_PRAGMA(x) _Pragma(#x)
-#define SONAR_UNROLL_ITEMS SONAR_PRAGMA(unroll SONAR_FFT_UNROLL)
-#ifndef SONAR_DRAW_UNROLL
-#define SONAR_DRAW_UNROLL 4  // the FFT kernel's draw loop: 1 / 2 / 4 measured 69.8 / 69 / 66.5 us per step at B=512; 8 spills (128-VGPR budget)
-#endif
-#ifndef SONAR_FFT_TW_LDS
-#define SONAR_FFT_TW_LDS 0  // measured: constant-memory (scalar) twiddles 78 us vs LDS table 125 us at B=512
-#endif
-#ifndef SONAR_FWD_UNI
-#define SONAR_FWD_UNI 1  // forward passes: wave-uniform twiddles through scalar loads (1) or as broadcast reads of the LDS table (0)
-#endif
-#ifndef SONAR_PW_SKIP
-#define SONAR_PW_SKIP 0  // profiling builds only (scratch/pw_passes.py): 1 draw, 2 column passes, 4 rows pass a, 8 rows pass b arithmetic, 16 global stores
-#endif
+// the FFT kernel's draw loop: unroll 1 / 2 / 4 measured 69.8 / 69 / 66.5 us per step at B=512; 8 spills (128-VGPR budget)
+constexpr int kDrawUnroll = 4;
 #ifdef SONAR_PW_TRACE  // profiling builds: per-phase s_memtime stamps of wave 0 of every workgroup (scratch/pw_trace.py)
 __device__ unsigned long long g_pw_trace[1024 * 8 * 12];
 #define SONAR_STAMP(slot) do { if (tid == 0 && pidx < 8 && blockIdx.x < 1024) g_pw_trace[(blockIdx.x * 8 + pidx) * 12 + (slot)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define SONAR_STAMP(slot) do { } while (0)
 #endif
-constexpr int kFftThreads = SONAR_FFT_THREADS;  // waves per block x two blocks per CU (LDS-bound)
+constexpr int kFftThreads = 512;  // waves per block x two blocks per CU (LDS-bound)
 // threads (= RNG thread slots) of a fixed-size plane's workgroup: 512 from 8192 values up, smaller planes take fewer so that
 // every pass has work for all of them (64 x 64: 256; 32 x 32: 128; 16 x 16: 64) and more workgroups share a CU
 template <int H, int W>
@@ -169,7 +142,7 @@ struct PlaneCfg {
     static constexpr int CN1 = split_n1(H), CN2 = H / CN1;
     // 64 x 64: rows of 32 complex values split 8 x 4, not 4 x 8 -- row pass b's RN1 lanes of a row store side by side, 64-byte runs
     // instead of 32 (79 -> 77.5 us generated, 95 -> 92 us filtered per 33.5 M values; the other heights with W = 64 do not gain)
-    static constexpr int RN1 = (H == 64 && M == 32 && SONAR_ROW32_SPLIT8) ? 8 : split_n1(M), RN2 = M / RN1;
+    static constexpr int RN1 = (H == 64 && M == 32) ? 8 : split_n1(M), RN2 = M / RN1;
     // Column of element (k1, n2) of a row BETWEEN the two row passes (inverse: written by pass a, read by pass b; forward: written by
     // pass b', read by pass a').  The natural k = RN2 k1 + n2 puts the RN1 lanes of a row that pass b runs side by side (k1 = lane %
     // RN1) RN2 complex values = 16 dwords apart: with S = 1 mod 16 the 16 lanes of an LDS access group (ds_read2_b64 / ds_write2_b64:
@@ -350,7 +323,7 @@ __device__ __forceinline__ void fill_plane_gen(const float* __restrict__ filter,
     auto fpos = [&](int p) { return (p >> LM) * Wh + 1 + (p & (M - 1)); };
     const int p0 = min(tid, PAIRS - 1);
     float fa = filter[fpos(p0)], fb = filter[fpos(p0) + (H / 2) * Wh];
-    draw_plane<H, W, true, SONAR_DRAW_UNROLL>(
+    draw_plane<H, W, true, kDrawUnroll>(
         g, tid,
         [&](uint32_t r0, uint32_t rm, uint32_t t) {
             T0[tid] = drawn_elem(r0, angle_lo(t), filter[tid * Wh]);
@@ -417,9 +390,6 @@ template <int H, int W, int NW, int LAYOUT = kRowsTwoBuffers>
 __device__ __forceinline__ void pipe_row_a(const c32* Y, c32* X, int w, int lane);
 template <int H, int W, int NW, bool STATS, bool NORM, int LAYOUT = kRowsTwoBuffers>
 __device__ __forceinline__ void pipe_row_b(const c32* X, float* oplane, int w, int lane, float scale, float nm, float nc, double& s, double& q);
-#ifndef SONAR_SF_V2
-#define SONAR_SF_V2 1  // 0: the round-4 forward half (separate split / unpack / fix-up phases: 12 barriers per plane instead of 7)
-#endif
 
 // Look-ahead of the phase-serial generate kernel (launch-bound batch sizes: every workgroup of the launch is resident at once): the
 // workgroups from `main_blocks` on compute the statistics of the NEXT call (stream `stream_id`, same seed / shape / filter) into

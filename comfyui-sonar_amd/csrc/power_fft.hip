@@ -24,7 +24,7 @@ namespace sonar {
 // shapes spilled 2-50 registers at 128): two waves per SIMD, one workgroup per CU.
 template <int H, int W>
 constexpr int plane_min_waves() {
-    return (H * W >= 32768 || (H == 256 && W == 64) || (H == 64 && W == 256) || (H == 64 && W == 32)) ? 2 : SONAR_FFT_WAVES;
+    return (H * W >= 32768 || (H == 256 && W == 64) || (H == 64 && W == 256) || (H == 64 && W == 32)) ? 2 : 4;
 }
 
 // SRC: 0 = spectrum `z` supplied (replay), 1 = spectrum drawn on device, 2 = `z` is a REAL H x W plane: forward r2c FFT in
@@ -43,7 +43,7 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
     // FAST shapes (W = 128, H = 64 / 128, 8 waves): every wave owns ONE residue n2 in both twiddled passes, so all
     // twiddles are wave-uniform AND loop-invariant -> loaded once into scalar registers before the plane loop
     // (no s_load / lgkmcnt(0) stall inside the passes); the column split is H = (H/8) x 8 instead of 8 x (H/8).
-    constexpr bool FAST = (W == 128) && (H == 128 || H == 64) && (NT == 512) && !SONAR_FFT_TW_LDS;
+    constexpr bool FAST = (W == 128) && (H == 128 || H == 64) && (NT == 512);
     constexpr int CN1 = FAST ? H / 8 : C::CN1, CN2 = FAST ? 8 : C::CN2;
     // (Measured dead end, round 3: fusing the spectral filter's last forward column pass, the filter and the inverse's first column pass
     // in registers -- the same 16 rows of a column per thread -- spills at the 128-register cap: 107 us instead of 94 per 512 latents.)
@@ -100,11 +100,9 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
     }
     double s = 0.0, q = 0.0;
     for (int j = tid; j < 256; j += NT) TW[j] = c_tw256[j];
-#if SONAR_FFT_TW_LDS
-    auto tw = [&](int idx, int n, bool) -> c32 { return TW[(idx * (256 / n)) & 255]; };
-#else
     // `uni`: the index is wave-uniform (lanes = consecutive columns / rows of one n2) -> scalar load
     // (a per-lane index reads the LDS copy: vector loads from constant memory cost 64-bit address registers)
+    // (measured: constant-memory (scalar) twiddles 78 us vs every twiddle from the LDS table 125 us at B=512)
     // (__device__ on the lambdas that name c_tw256: an unmarked lambda is host-callable as far as the compiler knows, a static table it names
     // becomes an external symbol, and every kernel of this file then fetched the table's ADDRESS through the global offset table -- one more
     // scalar-cache miss in front of the first twiddle, 576 sites; spectral filter 62.4 -> 61.8 us, 13.05 -> 12.7 us at batch 64)
@@ -112,7 +110,6 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
         if (uni) return c_tw256[(__builtin_amdgcn_readfirstlane(idx) * (256 / n)) & 255];
         return TW[(idx * (256 / n)) & 255];
     };
-#endif
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     c32 ctw[CN1], gtw[RN1], ptw[RN1];
@@ -126,10 +123,6 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
     };
     if constexpr (FAST) load_twiddles(wv);
 
-#ifdef SONAR_PW_DESYNC  // profiling builds: the second resident workgroup of every CU starts late (out of phase with the first)
-    if (blockIdx.x >= gridDim.x / 2)
-        for (int i = 0; i < SONAR_PW_DESYNC; ++i) __builtin_amdgcn_s_sleep(32);
-#endif
     [[maybe_unused]] int pidx = 0;  // planes this workgroup has started (trace builds)
     [[maybe_unused]] int edge_want = 0;
     if (tid == 0) edge_seq = 0;  // visible after the first plane's top-of-loop barrier
@@ -158,8 +151,8 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
         // passes at a higher issue priority the co-resident workgroup's draw fills their gaps instead of delaying them (-2.7 us per launch)
         __builtin_amdgcn_s_setprio(0);
         if constexpr (GEN) {
-            if constexpr (!(SONAR_PW_SKIP & 1)) fill_plane_gen<H, W, S>(filter, rng, tid, A, T0, TM, (FAST && H == 2 * 64) ? &edge_seq : nullptr);
-            if constexpr (FAST && H == 2 * 64 && !(SONAR_PW_SKIP & 1)) {
+            fill_plane_gen<H, W, S>(filter, rng, tid, A, T0, TM, (FAST && H == 2 * 64) ? &edge_seq : nullptr);
+            if constexpr (FAST && H == 2 * 64) {
                 // The edge columns were drawn first, by waves 0-1, which then announced themselves in edge_seq; the LAST two waves build
                 // the packed column 0 from them at the end of their own draws (Q[ky] = sym(Z0)[ky] + i sym(ZM)[ky]): no separate
                 // fix-up phase and barrier, and the edge work is not stacked on the waves that already drew it.
@@ -244,7 +237,7 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
                 const c32 a = row[k], b = row[M - k];
                 const c32 e = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y - b.y));
                 const c32 o = make_float2(0.5f * (a.y + b.y), -0.5f * (a.x - b.x));
-                const c32 t = cmulc(o, tw(k, W, SONAR_FWD_UNI && H % 64 == 0));
+                const c32 t = cmulc(o, tw(k, W, H % 64 == 0));
                 row[k] = make_float2(e.x + t.x, e.y + t.y);
                 row[M - k] = make_float2(e.x - t.x, -(e.y - t.y));
             }
@@ -258,7 +251,7 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
             for (int k2 = 0; k2 < CN2; ++k2) u[k2] = A[(CN2 * k1 + k2) * S + c];
             fdft<CN2>(u);
 #pragma unroll
-            for (int n2 = 1; n2 < CN2; ++n2) u[n2] = cmulc(u[n2], tw(n2 * k1, H, SONAR_FWD_UNI && M % 64 == 0));
+            for (int n2 = 1; n2 < CN2; ++n2) u[n2] = cmulc(u[n2], tw(n2 * k1, H, M % 64 == 0));
 #pragma unroll
             for (int n2 = 0; n2 < CN2; ++n2) A[(CN2 * k1 + n2) * S + c] = u[n2];
         }
@@ -282,7 +275,7 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
             T0[ky] = make_float2(0.5f * (p.x + pn.x) * f0, 0.5f * (p.y - pn.y) * f0);
             TM[ky] = make_float2(0.5f * (p.y + pn.y) * fm, -0.5f * (p.x - pn.x) * fm);
         }
-        if constexpr (SRC != 3 && !(FAST && SONAR_FILTER_IN_PASS)) {
+        if constexpr (SRC != 3 && !FAST) {
         // unrolled: the filter values are global loads (L2 hits) -- eight in flight instead of a wait per element
 #pragma unroll 8
         for (int j = ptid; j < H * M; j += NT) {
@@ -307,7 +300,7 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
         }
         }
         if constexpr (FAST) {
-            if constexpr (!(GEN && H == 2 * 64) || (SONAR_PW_SKIP & 1)) {
+            if constexpr (!(GEN && H == 2 * 64)) {
                 // fix-up: Q[ky] = sym(Z0)[ky] + i sym(ZM)[ky] -> column 0 of the plane (the 128-row generate path did it inside the fill)
                 if (tid < H) {
                     const int ky = tid, kn = (H - ky) & (H - 1);
@@ -318,10 +311,10 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
             }
             SONAR_STAMP(3);
             // ------------------------------------------------------------ columns, pass a: radix CN1, one item per thread
-            if constexpr (!(SONAR_PW_SKIP & 2)) {
+            {
                 const int c = lane, n2 = wv;
                 c32 v[CN1];
-                if constexpr (SRC == 2 && SONAR_FILTER_IN_PASS) {
+                if constexpr (SRC == 2) {
                     // the spectral filter's multiply rides on this pass's loads instead of being a pass over the plane of its own (column 0
                     // is the packed edge pair, filtered when it was unpacked).  The filter values are the same for every plane: an opaque
                     // lane index keeps their loads (L1 hits) in the plane loop -- hoisted they would hold CN1 registers the passes need.
@@ -350,14 +343,14 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
             if constexpr (H == 128) {
             // ------------------------------------------------------------ the pipelined kernel's passes: all LDS operands requested up
             // front, row pass a leaves element (k1, n2) at column 8 n2 + k1 for the 16-byte stores of pass b
-            if constexpr (!(SONAR_PW_SKIP & 2)) pipe_col_b<H, W, 8>(A, A, wv, lane);  // in place: an item reads and writes the same 8 rows of its column
+            pipe_col_b<H, W, 8>(A, A, wv, lane);  // in place: an item reads and writes the same 8 rows of its column
             __syncthreads();
-            if constexpr (!(SONAR_PW_SKIP & 4)) pipe_row_a<H, W, 8, kRowsInPlace>(A, A, wv, lane);
+            pipe_row_a<H, W, 8, kRowsInPlace>(A, A, wv, lane);
             __syncthreads();
             } else {
             // ------------------------------------------------------------ columns, pass b: radix 8, rows 8 k1 .. 8 k1 + 7
 #pragma unroll
-            for (int it = 0; it < ((SONAR_PW_SKIP & 2) ? 0 : CN1 / 8); ++it) {
+            for (int it = 0; it < CN1 / 8; ++it) {
                 const int c = lane, k1 = wv + 8 * it;
                 c32 u[CN2];
 #pragma unroll
@@ -370,7 +363,7 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
             __syncthreads();
             SONAR_STAMP(7);
             // ------------------------------------------------------------ rows, pass a: n2 = wave, rows lane + 64 it
-            if constexpr (!(SONAR_PW_SKIP & 4)) {
+            {
                 constexpr int ITEMS = H / 64;
                 const int n2 = wv;
                 c32 g[ITEMS][RN1];
@@ -412,7 +405,7 @@ __global__ void __launch_bounds__((plane_threads<H, W>()), (plane_min_waves<H, W
         // ---------------------------------------------------------------- columns, pass a
         // Column 0 is built on the fly from the raw kx = 0 / kx = M columns:
         //   Q[ky] = sym(Z0)[ky] + i sym(ZM)[ky],  sym(Z)[ky] = (Z[ky] + conj Z[-ky]) / 2
-SONAR_UNROLL_ITEMS
+#pragma unroll 1
         for (int item = ptid; item < CN2 * M; item += NT) {
             const int c = item % M;
             const int n2 = item / M;
@@ -437,7 +430,7 @@ SONAR_UNROLL_ITEMS
         __syncthreads();
         // ---------------------------------------------------------------- columns, pass b
         // LDS row r = CN2*k1 + k2 afterwards holds spatial row y = k1 + CN1*k2
-SONAR_UNROLL_ITEMS
+#pragma unroll 1
         for (int item = ptid; item < CN1 * M; item += NT) {
             const int c = item % M, k1 = item / M;
             c32 u[CN2];
@@ -529,14 +522,14 @@ SONAR_UNROLL_ITEMS
             continue;
         }
         float ps = 0.0f, pq = 0.0f;  // per-plane fp32 partials (<= 64 values per thread), folded into fp64 below
-SONAR_UNROLL_ITEMS
+#pragma unroll 1
         for (int item = ptid; item < RN1 * H; item += NT) {
             const int k1 = item % RN1, r = item / RN1;
             const int y = (r / CN2) + CN1 * (r % CN2);
             c32 u[RN2];
 #pragma unroll
-            for (int n2 = 0; n2 < RN2; ++n2) u[n2] = (SONAR_PW_SKIP & 8) ? make_float2((float)(item + n2), 1.0f) : A[r * S + C::rpos(k1, n2)];
-            if constexpr (!(SONAR_PW_SKIP & 8)) idft<RN2>(u);
+            for (int n2 = 0; n2 < RN2; ++n2) u[n2] = c32(A[r * S + C::rpos(k1, n2)]);  // (through a copy: assigned directly, ten statistics kernels swap two operand loads -- same values, other bytes)
+            idft<RN2>(u);
             float* orow = oplane + (int64_t)y * W;
 #pragma unroll
             for (int k2 = 0; k2 < RN2; ++k2) {
@@ -548,8 +541,7 @@ SONAR_UNROLL_ITEMS
                     a = u[k2].x * scale;
                     b = u[k2].y * scale;
                 }
-                if constexpr (!(SONAR_PW_SKIP & 16)) *reinterpret_cast<float2*>(orow + 2 * (k1 + RN1 * k2)) = make_float2(a, b);
-                else if (a == 123.456f && b == 654.321f) *reinterpret_cast<float2*>(orow) = make_float2(a, b);  // keeps the arithmetic alive
+                *reinterpret_cast<float2*>(orow + 2 * (k1 + RN1 * k2)) = make_float2(a, b);
                 if constexpr (STATS) {
                     ps += a + b;
                     pq = __builtin_fmaf(a, a, __builtin_fmaf(b, b, pq));
@@ -583,59 +575,24 @@ SONAR_UNROLL_ITEMS
 // While the drawing team works in registers the buffer of plane j is free: the transforming team ping-pongs between the buffers
 // (pass b: X -> Y, row pass a: Y -> X, no read-before-write barrier inside row pass a), and the drawing team writes plane j into Y in
 // the last phase, when nothing reads Y any more.  The hardware barrier counts all 16 waves: both teams run the SAME three barriers
-// per plane; the draw is cut into chunks of whole pair iterations that follow the transform phases' durations (SONAR_PIPE_CHUNKS =
+// per plane; the draw is cut into chunks of whole pair iterations that follow the transform phases' durations (kPipeChunks =
 // iterations in phases 1 and 2; the rest, with column pass a, in phase 3).  Thread slot = thread within the drawing team: streams,
 // draw order and arithmetic -- therefore every output bit -- are those of power_irfft2_kernel<H, W, 1, ...>.
-#ifndef SONAR_PIPE_NT
-#define SONAR_PIPE_NT 0  // profiling builds: the row pass's 16-byte stores with the non-temporal hint (64-byte runs per four lanes: slower, common.h)
-#endif
-#ifndef SONAR_PIPE_CHUNKS
-#define SONAR_PIPE_CHUNKS 0, 4  // round 5: 0 + 4 + 4 iterations per phase.  Re-swept at the round's end (`scratch/pipe_ab.py`, same box, us per call): 2 + 4 + 2 (the
-                                // setting while the draw was being shortened) 39.6; 1 + 4 + 3 39.5; 1 + 3 + 4 38.9; **0 + 4 + 4 38.6**; 0 + 5 + 3 39.2; 0 + 3 + 5 40.0; 0 + 6 + 2 39.8; 3 + 5 + 0 (round 4) 41.5+
-#endif
+// Round 5: 0 + 4 + 4 iterations per phase.  Measured when re-swept at the round's end (same box, us per call): 2 + 4 + 2 (the setting
+// while the draw was being shortened) 39.6; 1 + 4 + 3 39.5; 1 + 3 + 4 38.9; **0 + 4 + 4 38.6**; 0 + 5 + 3 39.2; 0 + 3 + 5 40.0;
+// 0 + 6 + 2 39.8; 3 + 5 + 0 (round 4) 41.5+
+constexpr int kPipeChunks[2] = {0, 4};
 // look-ahead statistics (TeamStats): planes of the unit whose radius words are drawn in the first / by the end of the second of the
 // three phases; A, B drawing team (while the last plane is transformed), C, D transforming team (while the first plane is drawn)
-#ifndef SONAR_AHEAD_SPLIT_A
-#define SONAR_AHEAD_SPLIT_A 1
-#define SONAR_AHEAD_SPLIT_B 3
-#endif
-#ifndef SONAR_AHEAD_SPLIT_C
-#define SONAR_AHEAD_SPLIT_C 2
-#define SONAR_AHEAD_SPLIT_D 3
-#endif
-#ifndef SONAR_AHEAD_PRIO
-#define SONAR_AHEAD_PRIO 0  // the transforming team's issue priority while it computes look-ahead statistics beside the first draw
-#endif
-// Measured and left off (round 5, gpurun_out/dc, profiles/r05_power_kernel.md): with SONAR_PIPE_DECOUPLE the teams meet at ONE workgroup
-// barrier per plane -- the transforming team's two exchanges inside an iteration become a team-only rendezvous (below), the drawing team
-// draws its plane in one stretch and only looks at the other team's counter before it writes -- same bits, no hang, and no faster:
-// 42.3-42.5 against 41.6-42.0 us per call, 39.4 = 39.4 us for the final pass alone (spinning at low priority, longer sleeps, equal
-// priorities: 42.5-43.8).  The three lock-step phases are not what bounds the kernel; its instruction streams are.
-#ifndef SONAR_PIPE_DECOUPLE
-#define SONAR_PIPE_DECOUPLE 0
-#endif
-// A team's own exchange (SONAR_PIPE_DECOUPLE): the hardware barrier counts all sixteen waves, so a team-only rendezvous is a counter in
-// LDS -- every wave's lane 0 adds one when the wave's LDS operations are complete (LDS executes a wave's operations in order, and the
-// waves' in arrival order: who sees the count sees what was written in front of it), then the wave polls until the count reaches
-// `target`.  team_wait alone is the other team looking at that counter.
-__device__ __forceinline__ void team_wait(const int* ctr, int target) {
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < target) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void team_barrier(int* ctr, int target, int lane) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    team_wait(ctr, target);
-}
-#ifndef SONAR_PIPE_PRIO_DRAW
-#define SONAR_PIPE_PRIO_DRAW 0
-#endif
-#ifndef SONAR_PIPE_PRIO_FFT
-#define SONAR_PIPE_PRIO_FFT 3
-#endif
-#ifndef SONAR_PIPE_SKIP
-#define SONAR_PIPE_SKIP 0  // profiling builds only: 1 no global stores, 2 no draw arithmetic (zeros), 4 no row pass b arithmetic, 8 no row pass a, 16 no column pass b
-#endif
+constexpr int kAheadSplitA = 1, kAheadSplitB = 3;
+constexpr int kAheadSplitC = 2, kAheadSplitD = 3;
+constexpr int kAheadPrio = 0;  // the transforming team's issue priority while it computes look-ahead statistics beside the first draw
+constexpr int kPipePrioDraw = 0, kPipePrioFft = 3;  // the teams' issue priorities
+// Measured and dropped (round 5, profiles/r05_power_kernel.md): a decoupled variant in which the teams met at ONE workgroup barrier per
+// plane -- the transforming team's two exchanges inside an iteration were a team-only rendezvous through a counter in LDS, the drawing
+// team drew its plane in one stretch and only looked at the other team's counter before it wrote -- gave the same bits, no hang, and was
+// no faster: 42.3-42.5 against 41.6-42.0 us per call, 39.4 = 39.4 us for the final pass alone (spinning at low priority, longer sleeps,
+// equal priorities: 42.5-43.8).  The three lock-step phases are not what bounds the kernel; its instruction streams are.
 #ifdef SONAR_PW_TRACE
 __device__ unsigned long long g_pipe_trace[256 * 16 * 10 * 4];
 #define SONAR_PIPE_STAMP(slot) do { if (lane == 0 && j < 10 && blockIdx.x < 256) g_pipe_trace[((blockIdx.x * 16 + wv_all) * 10 + j) * 4 + (slot)] = __builtin_readcyclecounter(); } while (0)
@@ -657,13 +614,8 @@ __device__ __forceinline__ void draw_chunk_regs(SpectrumRng& g, c32 (&v)[H / 8],
         const uint32_t ra = g.R.next();
         const uint32_t rb = g.R.next();
         const uint32_t t = g.T.next();
-        if constexpr (SONAR_PIPE_SKIP & 2) {
-            v[it] = make_float2(wa[it] + (float)ra, wb[it]);
-            v[it + H / 16] = make_float2(wb[it] + (float)t, wa[it] + (float)rb);
-        } else {
-            v[it] = drawn_weighted(ra, angle_lo(t), wa[it]);
-            v[it + H / 16] = drawn_weighted(rb, angle_hi(t), wb[it]);
-        }
+        v[it] = drawn_weighted(ra, angle_lo(t), wa[it]);
+        v[it + H / 16] = drawn_weighted(rb, angle_hi(t), wb[it]);
     }
 }
 // a filter with negative values (a wave that met one: uniform branch): the sign the weights dropped goes back on, read from the filter
@@ -865,16 +817,11 @@ __device__ __forceinline__ void pipe_row_b(const c32* X, float* oplane, int w, i
 #pragma unroll
     for (int n2 = 0; n2 < RN2; ++n2) {
 #pragma unroll
-        for (int i = 0; i < NK; ++i) {
-            if constexpr (SONAR_PIPE_SKIP & 4) u[i][n2] = make_float2((float)(lane + n2), 1.0f + i);
-            else u[i][n2] = X[r * S + (SWZ ? C::rpos(k0 + i, n2) : RN1 * n2 + k0 + i)];
-        }
+        for (int i = 0; i < NK; ++i) u[i][n2] = X[r * S + (SWZ ? C::rpos(k0 + i, n2) : RN1 * n2 + k0 + i)];
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!(SONAR_PIPE_SKIP & 4)) {
 #pragma unroll
-        for (int i = 0; i < NK; ++i) idft<RN2>(u[i]);
-    }
+    for (int i = 0; i < NK; ++i) idft<RN2>(u[i]);
     float* const orow = oplane + (int64_t)y * W + 2 * k0;
     float ps = 0.0f, pq = 0.0f;
 #pragma unroll
@@ -895,10 +842,8 @@ __device__ __forceinline__ void pipe_row_b(const c32* X, float* oplane, int w, i
             }
         }
         float* const dst = orow + 2 * RN1 * k2;
-        if constexpr (SONAR_PIPE_SKIP & 1) {
-            if (o[0] == 123.456f && o[1] == 654.321f) *reinterpret_cast<float2*>(dst) = make_float2(o[0], o[1]);  // keeps the arithmetic alive
-        } else if constexpr (NK == 2) {
-            store4<(SONAR_PIPE_NT != 0)>(dst, o[0], o[1], o[2], o[3]);
+        if constexpr (NK == 2) {
+            store4<false>(dst, o[0], o[1], o[2], o[3]);  // (measured slower with the non-temporal hint: 64-byte runs per four lanes, common.h)
         } else {
             *reinterpret_cast<float2*>(dst) = make_float2(o[0], o[1]);
         }
@@ -1091,15 +1036,6 @@ __device__ __forceinline__ void sf_col_a_filter_col_a(c32* A, SfExchange<H>* xch
 //   cols a' x filter, cols a   radix 16 forward, the filter, radix 16 inverse in registers (sf_col_a_filter_col_a; one barrier inside)
 //   cols b, rows a, rows b     the pipelined generate kernel's passes on the swizzled row layout (kRowsSwizzled: row pass a in place
 //              without the barrier between its loads and stores)
-#ifndef SONAR_SF_FILTER_EARLY
-#define SONAR_SF_FILTER_EARLY 1
-#endif
-#ifndef SONAR_SF_PREFETCH
-#define SONAR_SF_PREFETCH 1  // 0: a plane's loads are requested at its own start (A/B)
-#endif
-#ifndef SONAR_SF_WIDE
-#define SONAR_SF_WIDE 1  // rows b' takes items (k1 = 2 (t % 4) + i, LDS row t / 4) with eight 16-byte loads per thread; 0: (k1 = t % 8, LDS rows
-#endif                   // t / 8 + 64 i) with sixteen 8-byte ones (+1 us per 512 latents).  (Global accesses need dword alignment, whatever their width.)
 template <int H, int W, bool STATS>
 __global__ void __launch_bounds__(512, 4) spectral_filter128_kernel(const float* __restrict__ x, const float* __restrict__ filter, float* out, int64_t planes,
                                                                      double* partials) {
@@ -1126,29 +1062,19 @@ __global__ void __launch_bounds__(512, 4) spectral_filter128_kernel(const float*
         sums[NT + tid] = 0.0;
     }
     [[maybe_unused]] int pidx = 0;
-    // rows b': item (k1 = tid % 8, LDS row r = tid / 8 + 64 it); LDS row r holds spatial row y = r / 8 + 16 (r % 8) (what the column passes
-    // expect); complex element m = k1 + 8 k2 of a row is (x[2m], x[2m+1])
+    // rows b': items (k1 = 2 (tid % 4) + i, LDS row r = tid / 4) with eight 16-byte loads per thread (measured: items (k1 = tid % 8, LDS
+    // rows tid / 8 + 64 i) with sixteen 8-byte loads cost +1 us per 512 latents; global accesses need dword alignment, whatever their
+    // width); LDS row r holds spatial row y = r / 8 + 16 (r % 8) (what the column passes expect); complex element m = k1 + 8 k2 of a row
+    // is (x[2m], x[2m+1])
     c32 u[2][RN2];
-    constexpr bool WIDE = SONAR_SF_WIDE != 0;
     auto request = [&](int64_t plane, int t) {
-        if constexpr (WIDE) {
-            const int r = t >> 2, y = (r / CN2) + CN1 * (r % CN2);
-            const float* xrow = x + plane * (int64_t)H * W + (int64_t)y * W + 4 * (t & 3);
+        const int r = t >> 2, y = (r / CN2) + CN1 * (r % CN2);
+        const float* xrow = x + plane * (int64_t)H * W + (int64_t)y * W + 4 * (t & 3);
 #pragma unroll
-            for (int k2 = 0; k2 < RN2; ++k2) {
-                const float4 v = *reinterpret_cast<const float4*>(xrow + 2 * RN1 * k2);
-                u[0][k2] = make_float2(v.x, v.y);
-                u[1][k2] = make_float2(v.z, v.w);
-            }
-        } else {
-            const int k1 = t & 7;
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-                const int r = (t >> 3) + 64 * it, y = (r / CN2) + CN1 * (r % CN2);
-                const float* xrow = x + plane * (int64_t)H * W + (int64_t)y * W;
-#pragma unroll
-                for (int k2 = 0; k2 < RN2; ++k2) u[it][k2] = *reinterpret_cast<const float2*>(xrow + 2 * (k1 + RN1 * k2));
-            }
+        for (int k2 = 0; k2 < RN2; ++k2) {
+            const float4 v = *reinterpret_cast<const float4*>(xrow + 2 * RN1 * k2);
+            u[0][k2] = make_float2(v.x, v.y);
+            u[1][k2] = make_float2(v.z, v.w);
         }
     };
     // the inverse's last three passes (the next plane's loads are in flight through them)
@@ -1171,18 +1097,17 @@ __global__ void __launch_bounds__(512, 4) spectral_filter128_kernel(const float*
     };
     int64_t plane = blockIdx.x;
     if (plane >= planes) return;  // (never: the grid is at most `planes`)
-    if (SONAR_SF_PREFETCH) request(plane, tid);
+    request(plane, tid);
     for (;;) {
         __syncthreads();  // the previous plane's LDS reads are done (and the tables are visible)
         SONAR_STAMP(0);
         int ptid = tid;  // per plane: every LDS address of a plane is loop-invariant, and hoisted they spill (power_irfft2_kernel)
         asm volatile("" : "+v"(ptid));
         const int lane = ptid & 63;
-        if (!SONAR_SF_PREFETCH) request(plane, ptid);
         {
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
-                const int k1 = WIDE ? 2 * (ptid & 3) + it : ptid & 7, r = WIDE ? ptid >> 2 : (ptid >> 3) + 64 * it;
+                const int k1 = 2 * (ptid & 3) + it, r = ptid >> 2;
                 fdft<RN2>(u[it]);
 #pragma unroll
                 for (int n2 = 1; n2 < RN2; ++n2) u[it][n2] = cmulc(u[it][n2], TW[(n2 * k1) & (M - 1)]);
@@ -1196,11 +1121,10 @@ __global__ void __launch_bounds__(512, 4) spectral_filter128_kernel(const float*
         __syncthreads();
         SONAR_STAMP(2);
         float f[CN1];
-        if (SONAR_SF_FILTER_EARLY) sf_filter_values<H, W>(filter, wv, lane, f);  // a pass ahead of their use
+        sf_filter_values<H, W>(filter, wv, lane, f);  // a pass ahead of their use
         sf_col_b<H, W>(A, wv, lane);
         __syncthreads();
         SONAR_STAMP(3);
-        if (!SONAR_SF_FILTER_EARLY) sf_filter_values<H, W>(filter, wv, lane, f);
         sf_col_a_filter_col_a<H, W>(A, &xch, f, wv, lane, pidx);
         __syncthreads();
         SONAR_STAMP(4);
@@ -1211,7 +1135,7 @@ __global__ void __launch_bounds__(512, 4) spectral_filter128_kernel(const float*
             finish(plane, lane);
             break;
         }
-        if (SONAR_SF_PREFETCH) request(next, ptid);
+        request(next, ptid);
         finish(plane, lane);
         plane = next;
     }
@@ -1335,23 +1259,17 @@ __device__ __forceinline__ void pin_chunk(c32 (&v)[N]) {
     }
 }
 
-#ifndef SONAR_PIPE_KERNARG_TOUCH
-#define SONAR_PIPE_KERNARG_TOUCH 1
-#endif
 template <int H, int W, bool STATS, bool NORM>
 __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restrict__ filter, float* out, int64_t planes, uint64_t seed,
                                                           uint64_t stream_id, int64_t plane_offset, int group, int split, double* partials,
                                                           NormArgs na, uint64_t next_stream, double* partials_next) {
-#if SONAR_PIPE_KERNARG_TOUCH
     kernarg_touch_for(filter, out, planes, seed, stream_id, plane_offset, group, split, partials, na, next_stream, partials_next);
-#endif
     using C = PlaneCfg<H, W>;
     constexpr int NT = 512, NALL = 1024;
     static_assert(plane_threads<H, W>() == NT && W == 128 && H == 128, "one 8-wave team per plane, slot = one radix-16 column item");
     constexpr int M = C::M, S = C::S, Wh = M + 1, RN1 = C::RN1, RN2 = C::RN2, CN1 = H / 8, CN2 = 8, ITER = draw_iters<H, W>();
     constexpr int LM = draw_shift<W>();
-    constexpr int kChunk[2] = {SONAR_PIPE_CHUNKS};
-    constexpr int E0 = kChunk[0], E1 = E0 + kChunk[1];
+    constexpr int E0 = kPipeChunks[0], E1 = E0 + kPipeChunks[1];
     static_assert(E1 <= ITER && ITER == CN1 / 2, "chunks of whole pair iterations");
     constexpr int BUF = H * S;
     __shared__ c32 PLANES[2 * BUF];
@@ -1362,16 +1280,6 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
     static_assert(sizeof(uint4) * NT >= sizeof(c32) * 2 * H * kAheadMaxGroup, "edge columns of a look-ahead unit fit the seed area");
     __shared__ double sred[2 * NT / 64];  // wave sums of a team's look-ahead statistics (TeamStats)
     __shared__ double red[2 * NALL / 64];
-    // SONAR_PIPE_DECOUPLE: arrivals at the transforming team's exchanges (two per iteration: behind column pass b, behind row pass a) and
-    // at the drawing team's one (its look-ahead statistics)
-    __shared__ int tbar, dbar;
-    if constexpr (SONAR_PIPE_DECOUPLE) {
-        if (threadIdx.x == 0) {
-            tbar = 0;
-            dbar = 0;
-        }
-        __syncthreads();
-    }
     __shared__ NormDecision shd;
     const int wv_all = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const bool drawer = wv_all >= NT / 64;
@@ -1432,7 +1340,7 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
     double s = 0.0, q = 0.0;
     if (drawer) {
         // ------------------------------------------------------------------------------------------------ drawing team
-        __builtin_amdgcn_s_setprio(SONAR_PIPE_PRIO_DRAW);
+        __builtin_amdgcn_s_setprio(kPipePrioDraw);
         const c32* const Q = EDGE + 2 * H;  // the packed column 0 of the plane being drawn, left by the transforming team in phase 2
         SpectrumRng rng;
         // the slot's 16 filter weights, for every plane of the launch (and the look-ahead statistics of the epilogue)
@@ -1469,16 +1377,6 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
                 }
                 for (int i = 0; i < gw.first; ++i) skip_plane<H, W, true, false>(rng, tid);
             }
-            if constexpr (SONAR_PIPE_DECOUPLE) {
-                // the whole draw in one stretch: the only things this team needs from the other one are the free buffer (its row pass a
-                // has read Y) and the packed column -- both behind the transforming team's second exchange of this iteration
-                draw_chunk_regs<H, W, 0, ITER>(rng, v, wa, wb);
-                if (wave_neg) draw_chunk_signs<H, W, 0, ITER>(filter, tid, v);
-                pin_chunk<0, ITER>(v);
-                SONAR_PIPE_STAMP(1);
-                SONAR_PIPE_STAMP(2);
-                team_wait(&tbar, 2 * (NT / 64) * (j + 1));
-            } else {
             draw_chunk_regs<H, W, 0, E0>(rng, v, wa, wb);
             if (wave_neg) draw_chunk_signs<H, W, 0, E0>(filter, tid, v);
             pin_chunk<0, E0>(v);
@@ -1491,7 +1389,6 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
             __syncthreads();
             draw_chunk_regs<H, W, E1, ITER>(rng, v, wa, wb);
             if (wave_neg) draw_chunk_signs<H, W, E1, ITER>(filter, tid, v);
-            }
             if (lane == M - 1) {
 #pragma unroll
                 for (int n1 = 0; n1 < CN1; ++n1) v[n1] = Q[CN2 * n1 + wv];
@@ -1519,30 +1416,29 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
             c32* const edge = reinterpret_cast<c32*>(SEED_RT);
             const GroupWalk gw((int64_t)blockIdx.x + gridDim.x, group, split);
             ts.begin(filter, seed, next_stream, plane_offset, group, gw, tid, edge, wa, wb);
-            ts.radii(0, SONAR_AHEAD_SPLIT_A, tid);
+            ts.radii(0, kAheadSplitA, tid);
             SONAR_PIPE_STAMP(1);
-            if constexpr (SONAR_PIPE_DECOUPLE) team_barrier(&dbar, NT / 64, lane);  // the unit's edge columns are complete
-            else __syncthreads();
-            ts.radii(SONAR_AHEAD_SPLIT_A, SONAR_AHEAD_SPLIT_B, tid);
+            __syncthreads();  // the unit's edge columns are complete
+            ts.radii(kAheadSplitA, kAheadSplitB, tid);
             SONAR_PIPE_STAMP(2);
-            if constexpr (!SONAR_PIPE_DECOUPLE) __syncthreads();
-            ts.radii(SONAR_AHEAD_SPLIT_B, 4, tid);
+            __syncthreads();
+            ts.radii(kAheadSplitB, 4, tid);
             ts.products();
             ts.edges_and_wave_sums(edge, tid, sred);
             SONAR_PIPE_STAMP(3);
             __syncthreads();
         } else {
             SONAR_PIPE_STAMP(1);
-            if constexpr (!SONAR_PIPE_DECOUPLE) __syncthreads();
+            __syncthreads();
             SONAR_PIPE_STAMP(2);
-            if constexpr (!SONAR_PIPE_DECOUPLE) __syncthreads();
+            __syncthreads();
             SONAR_PIPE_STAMP(3);
             __syncthreads();
         }
     } else {
         // ------------------------------------------------------------------------------------------------ transforming team
         // wave wv owns residue n2 = wv in the twiddled row pass: every twiddle is wave-uniform and loop-invariant (scalar registers)
-        __builtin_amdgcn_s_setprio(SONAR_PIPE_PRIO_FFT);
+        __builtin_amdgcn_s_setprio(kPipePrioFft);
         int64_t unit = blockIdx.x;
         int gp = 0;
         // The two edge columns kx = 0, M of the plane being DRAWN are this team's (round 5; they were the drawing team's, which every
@@ -1590,11 +1486,7 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
         // second plane buffer, untouched until iteration 1), over the iteration's three barriers
         [[maybe_unused]] const int j = 0;  // (trace builds; shadowed by the loop below)
         SONAR_PIPE_STAMP(0);
-        int tb = 0;  // this team's exchanges so far
-        auto exchange = [&]() {
-            if constexpr (SONAR_PIPE_DECOUPLE) team_barrier(&tbar, (NT / 64) * ++tb, lane);
-            else __syncthreads();
-        };
+        auto exchange = [] { __syncthreads(); };  // the team's two exchanges inside an iteration: workgroup barriers, the drawing team runs the same
         if (ahead && my_units >= 1) {
             TeamStats<H, W> ts;
             c32* const edge = PLANES + BUF;
@@ -1604,24 +1496,24 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
                     partials_next[2 * slot] = 0.0;
                     partials_next[2 * slot + 1] = 0.0;
                 }
-            __builtin_amdgcn_s_setprio(SONAR_AHEAD_PRIO);
+            __builtin_amdgcn_s_setprio(kAheadPrio);
             draw_edges(0);
             ts.begin(filter, seed, next_stream, plane_offset, group, gw, tid, edge);
-            ts.radii(0, SONAR_AHEAD_SPLIT_C, tid);
+            ts.radii(0, kAheadSplitC, tid);
             SONAR_PIPE_STAMP(1);
             exchange();
             pack_edges(0);
-            ts.radii(SONAR_AHEAD_SPLIT_C, SONAR_AHEAD_SPLIT_D, tid);
+            ts.radii(kAheadSplitC, kAheadSplitD, tid);
             SONAR_PIPE_STAMP(2);
             exchange();
-            ts.radii(SONAR_AHEAD_SPLIT_D, 4, tid);
+            ts.radii(kAheadSplitD, 4, tid);
             ts.products();
             ts.edges_and_wave_sums(edge, tid, sred);
             leave_wave_sums();
             SONAR_PIPE_STAMP(3);
             __syncthreads();
             TeamStats<H, W>::store(sred, tid, partials_next, unit);
-            __builtin_amdgcn_s_setprio(SONAR_PIPE_PRIO_FFT);
+            __builtin_amdgcn_s_setprio(kPipePrioFft);
         } else {
             draw_edges(0);
             SONAR_PIPE_STAMP(1);
@@ -1639,12 +1531,12 @@ __global__ void __launch_bounds__(1024) power_pipe_kernel(const float* __restric
             c32* const X = PLANES + ((j + 1) & 1) * BUF;  // plane j - 1 (pass a's output)
             c32* const Y = PLANES + (j & 1) * BUF;        // free until the drawing team writes plane j in phase 3
             SONAR_PIPE_STAMP(0);
-            if (work && !(SONAR_PIPE_SKIP & 16)) pipe_col_b<H, W, NW>(X, Y, wv, lane);
+            if (work) pipe_col_b<H, W, NW>(X, Y, wv, lane);
             draw_edges(j);
             if (j == 1) decide_in_wave0();
             SONAR_PIPE_STAMP(1);
             exchange();
-            if (work && !(SONAR_PIPE_SKIP & 8)) pipe_row_a<H, W, NW>(Y, X, wv, lane);
+            if (work) pipe_row_a<H, W, NW>(Y, X, wv, lane);
             pack_edges(j);
             SONAR_PIPE_STAMP(2);
             exchange();
@@ -1788,8 +1680,7 @@ static int power_grid(int64_t planes, bool owns_partials = true) {
     static_assert(C::kLdsBytes + 256 <= 160 * 1024, "plane does not fit in LDS");
     // blocks/CU by LDS; persistent grid of resident blocks (<= kNPart when each owns a partial slot)
     // 16 waves per CU at the 128-row kernels' 128-VGPR budget; the smaller planes' kernels take 64 registers: 32 waves
-    static const int waves = [] { const char* e = getenv("SONAR_POWER_WAVES"); return e ? atoi(e) : 0; }();
-    const int threads_cu = waves > 0 ? waves * 64 : (H >= 128 ? 1024 : 2048);
+    const int threads_cu = H >= 128 ? 1024 : 2048;
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(threads_cu / plane_threads<H, W>(), (160 * 1024) / (C::kLdsBytes + 256)));
     const int64_t g = std::min<int64_t>(planes, (int64_t)256 * per_cu);
     return (int)(owns_partials ? std::min<int64_t>(g, kNPart) : g);
@@ -1844,7 +1735,7 @@ static int launch_power(int what, const float* z, const float* filter, float* ou
     if (what == 4) {
         SONAR_PW(3, false, false, nullptr);
     } else if (what == 3) {
-        if constexpr (H == 128 && W == 128 && SONAR_SF_V2) {
+        if constexpr (H == 128 && W == 128) {  // (seven barriers per plane; the general kernel's separate split / unpack / fix-up phases: twelve)
             const dim3 grid(power_grid<H, W>(planes, partials != nullptr));
             if (partials) hipLaunchKernelGGL((spectral_filter128_kernel<H, W, true>), grid, blk, 0, st, z, filter, out, planes, partials);
             else hipLaunchKernelGGL((spectral_filter128_kernel<H, W, false>), grid, blk, 0, st, z, filter, out, planes, partials);

@@ -36,15 +36,12 @@ void lds_attr(const void* kern, int bytes) {
     // text is kept for sonar_last_error(); the launch that follows reports the failure itself through check_launch).
     static std::mutex mu;
     static std::map<std::pair<const void*, int>, int> done;  // (kernel, device) -> bytes granted
-    static const bool always = [] { const char* e = getenv("SONAR_LDS_ATTR_ALWAYS"); return e && e[0] == '1'; }();  // (A/B of the per-launch form)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) (void)hipGetLastError();
     std::lock_guard<std::mutex> lock(mu);
     const std::pair<const void*, int> key{kern, dev};
-    if (!always) {
-        const auto it = done.find(key);
-        if (it != done.end() && it->second >= bytes) return;
-    }
+    const auto it = done.find(key);
+    if (it != done.end() && it->second >= bytes) return;
     const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();

@@ -1,4 +1,4 @@
-"""A/B of store hints in the elementwise kernels (SONAR_HIP_LIB picks the build): the Euler momentum step at 512 / 64 / 4 latents and cfg5's shard step."""
+"""Times of the elementwise kernels (SONAR_HIP_LIB picks the build; written for the A/B of their store hints): the Euler momentum step at 512 / 64 / 4 latents and cfg5's shard step."""
 import importlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, sonar_pkg
