@@ -1,0 +1,459 @@
+// SonarCustomNoiseParameters (py/noise.py:2080-2187): everything the item does to the inner sampler's tensor, two launches and no host
+// synchronisation.  The tensor is `planes` planes of `plane_in` values of which the first `plane_out` of each are kept (the square plane
+// of ensure_square_aspect_ratio cropped back; plane_in == plane_out without it: the entry points then see one plane of n values).
+//   scan:   one sweep over the generated tensor -> one slot of six 64-bit partials per block: the finite extremes over ALL values (the
+//           padding of a squared plane included: fix_invalid runs before the crop; two floats in one word); over the KEPT values the sum
+//           and sum of squares of the finite ones and the counts of +inf, -inf and NaN.
+//   apply:  every block reduces the slots (scale_noise_kernel's decide_norm, with more columns), from which the replacement values
+//           posval = max(largest finite, 0), negval = min(smallest finite, 0) (nan_to_num's extremes are taken AFTER the non-finite values
+//           became 0) and the statistics of the fixed, cropped tensor follow without a second read: sum += n+ posval + n- negval, sumsq
+//           += n+ posval^2 + n- negval^2.  Then per kept value: fix -> the two thresholded corrections (py/utils.py:100-105; the mean is
+//           subtracted as two floats) -> * factor -> one rounding into the output dtype, written at p * plane_out + i.
+// Source and output are fp32, fp16 or bf16 each; arithmetic is fp32, sums fp64 (sonar_stats_f32's form: for a mean-300 / std-1 tensor of
+// 2^20 values the cancellation in sumsq - sum * mean leaves the variance good to 1e-8).  HBM-bound: two reads of the source and one write.  A
+// work unit is one tile of kBlock * V values of ONE plane (so a lane never divides: the unit's plane is one uniform division per tile);
+// V = 4 -- one 16-byte access of fp32, 8 bytes of a half type -- when both plane lengths are multiples of 4 and the buffers are 16-byte
+// aligned (every plane then starts aligned and a vector is wholly kept or wholly padding), V = 1 otherwise, chosen per launch.  Tiles
+// that lie wholly inside the kept part run unguarded, two at a time; a plane's last tile checks its lanes.
+#include <math.h>
+
+#include <algorithm>
+
+#include "common.h"
+
+namespace sonar {
+namespace {
+
+constexpr int kSlot = SONAR_NOISE_PARAMS_SLOT;
+enum { S_SUM, S_SQ, S_POS, S_NEG, S_NAN, S_EXT };  // S_EXT: the finite maximum and minimum as two floats in one 64-bit word
+constexpr int kSums = S_EXT;
+static_assert(S_EXT + 1 == kSlot, "a slot holds the five sums and the pair of extremes");
+
+__device__ __forceinline__ double pack_ext(float mx, float mn) {
+    return __longlong_as_double((long long)(((uint64_t)__float_as_uint(mx) << 32) | (uint64_t)__float_as_uint(mn)));
+}
+__device__ __forceinline__ void unpack_ext(double w, float& mx, float& mn) {
+    const uint64_t b = (uint64_t)__double_as_longlong(w);
+    mx = __uint_as_float((uint32_t)(b >> 32));
+    mn = __uint_as_float((uint32_t)b);
+}
+
+// 16-bit storage types (bit patterns; arithmetic is fp32), as in cfg_op.hip
+struct H16 {
+    uint16_t bits;
+};
+struct B16 {
+    uint16_t bits;
+};
+
+__device__ __forceinline__ float widen(float v) { return v; }
+__device__ __forceinline__ float widen(H16 v) { return (float)__builtin_bit_cast(_Float16, v.bits); }
+__device__ __forceinline__ float widen(B16 v) { return __uint_as_float((uint32_t)v.bits << 16); }
+
+template <typename T>
+__device__ __forceinline__ T narrow(float v);
+template <>
+__device__ __forceinline__ float narrow<float>(float v) { return v; }
+template <>
+__device__ __forceinline__ H16 narrow<H16>(float v) { return H16{__builtin_bit_cast(uint16_t, (_Float16)v)}; }  // nearest even
+template <>
+__device__ __forceinline__ B16 narrow<B16>(float v) {  // nearest even; NaN -> the quiet NaN torch writes
+    const uint32_t u = __float_as_uint(v);
+    if (v != v) return B16{0x7FC0};
+    return B16{(uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16)};
+}
+
+template <int V>
+struct Vals {
+    float v[V];
+};
+
+template <int V, typename T>
+__device__ __forceinline__ Vals<V> load_vals(const T* p, int64_t i) {
+    Vals<V> r;
+    if constexpr (V == 1) {
+        r.v[0] = widen(p[i]);
+    } else if constexpr (sizeof(T) == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p + i);
+        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else {
+        const uint2 t = *reinterpret_cast<const uint2*>(p + i);
+        r.v[0] = widen(T{(uint16_t)(t.x & 0xFFFFu)}); r.v[1] = widen(T{(uint16_t)(t.x >> 16)});
+        r.v[2] = widen(T{(uint16_t)(t.y & 0xFFFFu)}); r.v[3] = widen(T{(uint16_t)(t.y >> 16)});
+    }
+    return r;
+}
+
+template <int V, typename T>
+__device__ __forceinline__ void store_vals(T* p, int64_t i, const Vals<V>& r) {
+    if constexpr (V == 1) {
+        p[i] = narrow<T>(r.v[0]);
+    } else if constexpr (sizeof(T) == 4) {
+        *reinterpret_cast<float4*>(p + i) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    } else {
+        uint2 t;
+        t.x = (uint32_t)narrow<T>(r.v[0]).bits | ((uint32_t)narrow<T>(r.v[1]).bits << 16);
+        t.y = (uint32_t)narrow<T>(r.v[2]).bits | ((uint32_t)narrow<T>(r.v[3]).bits << 16);
+        *reinterpret_cast<uint2*>(p + i) = t;
+    }
+}
+
+__device__ __forceinline__ bool finite_f(float y) { return fabsf(y) < INFINITY; }  // false for NaN
+
+// what one thread has seen
+struct Seen {
+    double s = 0.0, q = 0.0;
+    uint32_t npos = 0, nneg = 0, nnan = 0;
+    float mx = -INFINITY, mn = INFINITY;
+    // FIX: the finite / non-finite split; otherwise plain (sum, sumsq) of the kept values, whatever they are (scale_noise's statistics)
+    template <bool FIX>
+    __device__ __forceinline__ void add(float y, bool kept) {
+        if constexpr (FIX) {
+            const bool fin = finite_f(y);
+            mx = fmaxf(mx, fin ? y : -INFINITY);
+            mn = fminf(mn, fin ? y : INFINITY);
+            const double d = fin && kept ? (double)y : 0.0;
+            s += d;
+            q += d * d;
+            const bool bad = !fin && kept;
+            nnan += bad && y != y ? 1u : 0u;
+            npos += bad && y > 0.0f ? 1u : 0u;
+            nneg += bad && y < 0.0f ? 1u : 0u;
+        } else {
+            const double d = kept ? (double)y : 0.0;
+            s += d;
+            q += d * d;
+        }
+    }
+};
+
+// the five sums and the extremes of a block, folded over its threads; valid in thread 0.  `red`: kSlot * kBlock / 64 doubles
+__device__ __forceinline__ void block_fold(double (&sum)[kSums], float& mx, float& mn, double* red) {
+    constexpr int NW = kBlock / 64;
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) sum[k] = wave_sum(sum[k]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        mn = fminf(mn, __shfl_xor(mn, off, 64));
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) red[k * NW + wid] = sum[k];
+        red[S_EXT * NW + wid] = pack_ext(mx, mn);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) {
+            double a = red[k * NW];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) a += red[k * NW + w];
+            sum[k] = a;
+        }
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            float a, b;
+            unpack_ext(red[S_EXT * NW + w], a, b);
+            mx = fmaxf(mx, a);
+            mn = fminf(mn, b);
+        }
+    }
+}
+
+// units = planes * chunks tiles of kBlock * V source values; grid <= SONAR_NOISE_PARAMS_NPART, block b owns slot b
+template <int V, typename T, bool FIX>
+__global__ void __launch_bounds__(kBlock) noise_params_scan_kernel(const T* __restrict__ src, int64_t plane_in, int64_t plane_out, uint32_t chunks,
+                                                                   uint32_t units, double* __restrict__ partials) {
+    kernarg_touch_for(src, plane_in, plane_out, chunks, units, partials);
+    __shared__ double red[kSlot * kBlock / 64];
+    constexpr int64_t kTile = (int64_t)kBlock * V;
+    // without FIX the padding is of no interest: a plane ends at plane_out
+    const int64_t extent = FIX ? plane_in : plane_out;
+    Seen seen;
+    const uint32_t step = gridDim.x;
+    auto whole = [&](uint32_t u, int64_t& at) {  // the tile lies inside the kept part of its plane: no lane checks
+        const uint32_t p = u / chunks, c = u - p * chunks;
+        at = (int64_t)p * plane_in + (int64_t)c * kTile + (int64_t)threadIdx.x * V;
+        return ((int64_t)c + 1) * kTile <= plane_out;
+    };
+    auto guarded = [&](uint32_t u) {
+        const uint32_t p = u / chunks, c = u - p * chunks;
+        const int64_t i = (int64_t)c * kTile + (int64_t)threadIdx.x * V;
+        if (i < extent) {  // V == 4: both plane lengths are multiples of 4, the vector is inside, and wholly kept or wholly padding
+            const Vals<V> a = load_vals<V>(src, (int64_t)p * plane_in + i);
+#pragma unroll
+            for (int k = 0; k < V; ++k) seen.add<FIX>(a.v[k], i < plane_out);
+        }
+    };
+    uint32_t u = blockIdx.x;
+    for (; u < units; u += 2 * step) {
+        int64_t at0, at1 = 0;
+        const bool w0 = whole(u, at0);
+        const bool two = u + step < units && u + step > u;
+        const bool w1 = two && whole(u + step, at1);
+        if (w0 && w1) {  // two independent loads in flight
+            const Vals<V> a = load_vals<V>(src, at0), b = load_vals<V>(src, at1);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                seen.add<FIX>(a.v[k], true);
+                seen.add<FIX>(b.v[k], true);
+            }
+            continue;
+        }
+        if (w0) {
+            const Vals<V> a = load_vals<V>(src, at0);
+#pragma unroll
+            for (int k = 0; k < V; ++k) seen.add<FIX>(a.v[k], true);
+        } else {
+            guarded(u);
+        }
+        if (two) {
+            if (w1) {
+                const Vals<V> b = load_vals<V>(src, at1);
+#pragma unroll
+                for (int k = 0; k < V; ++k) seen.add<FIX>(b.v[k], true);
+            } else {
+                guarded(u + step);
+            }
+        }
+    }
+    double sum[kSums] = {seen.s, seen.q, (double)seen.npos, (double)seen.nneg, (double)seen.nnan};
+    block_fold(sum, seen.mx, seen.mn, red);
+    if (threadIdx.x == 0) {
+        double* slot = partials + (int64_t)blockIdx.x * kSlot;
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) slot[k] = sum[k];
+        slot[S_EXT] = pack_ext(seen.mx, seen.mn);
+    }
+}
+
+// what every block of the apply launch derives from the slots
+struct TailDecision {
+    NormDecision norm;
+    float mean_lo;  // mean - (float)mean: subtracted after norm.mean, so that a value next to the mean keeps its relative accuracy
+    float posval, negval;
+};
+
+// units = planes * chunks tiles of kBlock * V KEPT values
+template <int V, typename TS, typename TD>
+__global__ void __launch_bounds__(kBlock) noise_params_apply_kernel(const TS* __restrict__ src, TD* __restrict__ out, int64_t plane_in,
+                                                                    int64_t plane_out, uint32_t chunks, uint32_t units, int fix, int normalized,
+                                                                    float factor, float thr_sd, const double* __restrict__ partials, int npart,
+                                                                    int64_t n_total) {
+    kernarg_touch_for(src, out, plane_in, plane_out, chunks, units, fix, normalized, factor, thr_sd, partials, npart, n_total);
+    __shared__ double red[kSlot * kBlock / 64];
+    __shared__ TailDecision sh;
+    TailDecision t{NormDecision{0.f, 1.f, 0, 0}, 0.f, 0.f, 0.f};
+    if (partials != nullptr) {
+        double col[kSums] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        float mx = -INFINITY, mn = INFINITY;
+        for (int i = threadIdx.x; i < npart; i += kBlock) {
+            const double* slot = partials + (int64_t)i * kSlot;
+#pragma unroll
+            for (int k = 0; k < kSums; ++k) col[k] += slot[k];
+            float a, b;
+            unpack_ext(slot[S_EXT], a, b);
+            mx = fmaxf(mx, a);
+            mn = fminf(mn, b);
+        }
+        block_fold(col, mx, mn, red);
+        if (threadIdx.x == 0) {
+            // the extremes nan_to_num_ is handed are those of the tensor whose non-finite values are 0 already
+            t.posval = fmaxf(mx, 0.0f);
+            t.negval = fminf(mn, 0.0f);
+            if (normalized) {
+                const double pv = t.posval, nv = t.negval;
+                const double s = col[S_SUM] + col[S_POS] * pv + col[S_NEG] * nv;
+                const double q = col[S_SQ] + col[S_POS] * (pv * pv) + col[S_NEG] * (nv * nv);
+                t.norm = decision_from_totals(s, q, n_total, thr_sd);
+                const double lo = s * rcp_f64((double)n_total) - (double)t.norm.mean;  // (the mean as decision_from_totals forms it)
+                t.mean_lo = lo == lo && fabs(lo) < 1.0 ? (float)lo : 0.0f;              // a NaN / infinite mean has no low part
+            }
+            sh = t;
+        }
+        __syncthreads();
+        t = sh;
+    }
+    const NormDecision d = t.norm;
+    const bool do_mul = factor != 1.0f;
+    auto f = [&](float y) {
+        if (fix && !finite_f(y)) y = y != y ? 0.0f : (y > 0.0f ? t.posval : t.negval);
+        // scale_noise's sequence (common.h apply_norm) with the mean as two floats: y - mean is exact for y next to the mean, and what
+        // float32 dropped from the mean would otherwise be that result's whole error (3e-8 absolute on a value of 4e-7: four bfloat16 ulps)
+        if (d.do_sub) y = (y - d.mean) - t.mean_lo;
+        if (d.do_div) y = y / d.stdv;
+        if (do_mul) y = y * factor;
+        return y;
+    };
+    constexpr int64_t kTile = (int64_t)kBlock * V;
+    const uint32_t step = gridDim.x;
+    auto place = [&](uint32_t u, int64_t& from, int64_t& to) {  // true: the whole tile is kept
+        const uint32_t p = u / chunks, c = u - p * chunks;
+        const int64_t i = (int64_t)c * kTile + (int64_t)threadIdx.x * V;
+        from = (int64_t)p * plane_in + i;
+        to = (int64_t)p * plane_out + i;
+        return ((int64_t)c + 1) * kTile <= plane_out;
+    };
+    auto one = [&](int64_t from, int64_t to) {
+        Vals<V> a = load_vals<V>(src, from);
+#pragma unroll
+        for (int k = 0; k < V; ++k) a.v[k] = f(a.v[k]);
+        store_vals<V>(out, to, a);
+    };
+    auto guarded = [&](uint32_t u) {
+        const uint32_t p = u / chunks, c = u - p * chunks;
+        const int64_t i = (int64_t)c * kTile + (int64_t)threadIdx.x * V;
+        if (i < plane_out) one((int64_t)p * plane_in + i, (int64_t)p * plane_out + i);  // V == 4: plane_out is a multiple of 4
+    };
+    for (uint32_t u = blockIdx.x; u < units; u += 2 * step) {
+        int64_t f0, t0, f1 = 0, t1 = 0;
+        const bool w0 = place(u, f0, t0);
+        const bool two = u + step < units && u + step > u;
+        const bool w1 = two && place(u + step, f1, t1);
+        if (w0 && w1) {
+            Vals<V> a = load_vals<V>(src, f0), b = load_vals<V>(src, f1);
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                a.v[k] = f(a.v[k]);
+                b.v[k] = f(b.v[k]);
+            }
+            store_vals<V>(out, t0, a);
+            store_vals<V>(out, t1, b);
+            continue;
+        }
+        if (w0) one(f0, t0);
+        else guarded(u);
+        if (two) {
+            if (w1) one(f1, t1);
+            else guarded(u + step);
+        }
+    }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// tiles of `extent` values per plane at vector width v; false: more tiles than a 32-bit unit index holds
+inline bool tiling(int64_t planes, int64_t extent, int v, uint32_t& chunks, uint32_t& units) {
+    const int64_t tile = (int64_t)kBlock * v;
+    const int64_t c = (extent + tile - 1) / tile;
+    if (c > INT32_MAX || planes > INT32_MAX / c) return false;
+    chunks = (uint32_t)c;
+    units = (uint32_t)(planes * c);
+    return true;
+}
+
+struct ScanShape {
+    int v;
+    uint32_t chunks, units;
+    int grid;
+};
+
+// the scan launch's shape from what BOTH entry points are told (the apply launch reduces exactly the slots the scan wrote)
+inline bool scan_shape(const void* src, int64_t planes, int64_t plane_in, int64_t plane_out, int fix, ScanShape& s) {
+    s.v = (plane_in % 4 == 0 && plane_out % 4 == 0 && aligned16(src)) ? 4 : 1;
+    if (!tiling(planes, fix ? plane_in : plane_out, s.v, s.chunks, s.units)) return false;
+    s.grid = (int)std::min<uint32_t>(s.units, SONAR_NOISE_PARAMS_NPART);
+    return true;
+}
+
+// one plane of n values when nothing is cropped
+inline void flatten_planes(int64_t& planes, int64_t& plane_in, int64_t& plane_out) {
+    if (plane_in == plane_out) {
+        plane_in = plane_out = planes * plane_in;
+        planes = 1;
+    }
+}
+
+inline bool shape_ok(int64_t planes, int64_t plane_in, int64_t plane_out) {
+    return planes >= 0 && plane_out > 0 && plane_out <= plane_in && (planes == 0 || plane_in <= INT64_MAX / planes);
+}
+
+template <typename T>
+int scan_typed(const void* src, int64_t plane_in, int64_t plane_out, int fix, const ScanShape& s, double* partials, hipStream_t st) {
+    const dim3 grid(s.grid), block(kBlock);
+#define SONAR_NP_SCAN(V, FIX) \
+    hipLaunchKernelGGL((noise_params_scan_kernel<V, T, FIX>), grid, block, 0, st, (const T*)src, plane_in, plane_out, s.chunks, s.units, partials)
+    if (s.v == 4) {
+        if (fix) SONAR_NP_SCAN(4, true);
+        else SONAR_NP_SCAN(4, false);
+    } else {
+        if (fix) SONAR_NP_SCAN(1, true);
+        else SONAR_NP_SCAN(1, false);
+    }
+#undef SONAR_NP_SCAN
+    return check_launch("sonar_noise_params_scan");
+}
+
+template <typename TS, typename TD>
+int apply_typed(const void* src, void* out, int64_t planes, int64_t plane_in, int64_t plane_out, int fix, int normalized, float factor,
+                float thr_sd, const double* partials, int npart, bool vec, hipStream_t st) {
+    uint32_t chunks, units;
+    SONAR_REQUIRE(tiling(planes, plane_out, vec ? 4 : 1, chunks, units), SONAR_ERR_ARG, "sonar_noise_params_apply: too many tiles");
+    const dim3 grid((unsigned)std::min<uint32_t>(units, (uint32_t)kMaxGrid)), block(kBlock);
+    const int64_t n_total = planes * plane_out;
+    if (vec)
+        hipLaunchKernelGGL((noise_params_apply_kernel<4, TS, TD>), grid, block, 0, st, (const TS*)src, (TD*)out, plane_in, plane_out, chunks, units,
+                           fix, normalized, factor, thr_sd, partials, npart, n_total);
+    else
+        hipLaunchKernelGGL((noise_params_apply_kernel<1, TS, TD>), grid, block, 0, st, (const TS*)src, (TD*)out, plane_in, plane_out, chunks, units,
+                           fix, normalized, factor, thr_sd, partials, npart, n_total);
+    return check_launch("sonar_noise_params_apply");
+}
+
+template <typename TS>
+int apply_src(int dst_dtype, const void* src, void* out, int64_t planes, int64_t plane_in, int64_t plane_out, int fix, int normalized, float factor,
+              float thr_sd, const double* partials, int npart, bool vec, hipStream_t st) {
+    if (dst_dtype == SONAR_DTYPE_F32) return apply_typed<TS, float>(src, out, planes, plane_in, plane_out, fix, normalized, factor, thr_sd, partials, npart, vec, st);
+    if (dst_dtype == SONAR_DTYPE_F16) return apply_typed<TS, H16>(src, out, planes, plane_in, plane_out, fix, normalized, factor, thr_sd, partials, npart, vec, st);
+    return apply_typed<TS, B16>(src, out, planes, plane_in, plane_out, fix, normalized, factor, thr_sd, partials, npart, vec, st);
+}
+
+}  // namespace
+}  // namespace sonar
+
+using namespace sonar;
+
+extern "C" int64_t sonar_noise_params_ws_doubles(void) { return (int64_t)SONAR_NOISE_PARAMS_NPART * SONAR_NOISE_PARAMS_SLOT; }
+
+extern "C" int sonar_noise_params_scan(int src_dtype, const void* src, int64_t planes, int64_t plane_in, int64_t plane_out, int fix_invalid,
+                                       double* partials, void* stream) {
+    SONAR_REQUIRE(src_dtype >= SONAR_DTYPE_F32 && src_dtype <= SONAR_DTYPE_BF16, SONAR_ERR_ARG, "sonar_noise_params_scan: unknown dtype %d", src_dtype);
+    SONAR_REQUIRE(shape_ok(planes, plane_in, plane_out), SONAR_ERR_ARG, "sonar_noise_params_scan: bad planes / plane_in / plane_out");
+    if (planes == 0) return SONAR_OK;
+    SONAR_REQUIRE(src && partials, SONAR_ERR_ARG, "sonar_noise_params_scan: null pointer");
+    flatten_planes(planes, plane_in, plane_out);
+    ScanShape s;
+    SONAR_REQUIRE(scan_shape(src, planes, plane_in, plane_out, fix_invalid != 0, s), SONAR_ERR_ARG, "sonar_noise_params_scan: too many tiles");
+    const hipStream_t st = (hipStream_t)stream;
+    if (src_dtype == SONAR_DTYPE_F32) return scan_typed<float>(src, plane_in, plane_out, fix_invalid != 0, s, partials, st);
+    if (src_dtype == SONAR_DTYPE_F16) return scan_typed<H16>(src, plane_in, plane_out, fix_invalid != 0, s, partials, st);
+    return scan_typed<B16>(src, plane_in, plane_out, fix_invalid != 0, s, partials, st);
+}
+
+extern "C" int sonar_noise_params_apply(int src_dtype, const void* src, int dst_dtype, void* out, int64_t planes, int64_t plane_in,
+                                        int64_t plane_out, int fix_invalid, int normalized, float factor, float threshold_std_devs,
+                                        const double* partials, void* stream) {
+    SONAR_REQUIRE(src_dtype >= SONAR_DTYPE_F32 && src_dtype <= SONAR_DTYPE_BF16 && dst_dtype >= SONAR_DTYPE_F32 && dst_dtype <= SONAR_DTYPE_BF16,
+                  SONAR_ERR_ARG, "sonar_noise_params_apply: unknown dtype %d / %d", src_dtype, dst_dtype);
+    SONAR_REQUIRE(shape_ok(planes, plane_in, plane_out), SONAR_ERR_ARG, "sonar_noise_params_apply: bad planes / plane_in / plane_out");
+    const int fix = fix_invalid != 0, norm = normalized != 0;
+    SONAR_REQUIRE(partials || !(fix || norm), SONAR_ERR_ARG, "sonar_noise_params_apply: fix_invalid / normalized need the scan launch's partials");
+    if (planes == 0) return SONAR_OK;
+    SONAR_REQUIRE(src && out && src != out, SONAR_ERR_ARG, "sonar_noise_params_apply: null pointer, or out is src");
+    flatten_planes(planes, plane_in, plane_out);
+    int npart = 0;
+    ScanShape s{};
+    if (fix || norm) {
+        SONAR_REQUIRE(scan_shape(src, planes, plane_in, plane_out, fix, s), SONAR_ERR_ARG, "sonar_noise_params_apply: too many tiles");
+        npart = s.grid;
+    } else {
+        partials = nullptr;
+    }
+    const bool vec = plane_in % 4 == 0 && plane_out % 4 == 0 && aligned16(src) && aligned16(out);
+    const hipStream_t st = (hipStream_t)stream;
+    if (src_dtype == SONAR_DTYPE_F32) return apply_src<float>(dst_dtype, src, out, planes, plane_in, plane_out, fix, norm, factor, threshold_std_devs, partials, npart, vec, st);
+    if (src_dtype == SONAR_DTYPE_F16) return apply_src<H16>(dst_dtype, src, out, planes, plane_in, plane_out, fix, norm, factor, threshold_std_devs, partials, npart, vec, st);
+    return apply_src<B16>(dst_dtype, src, out, planes, plane_in, plane_out, fix, norm, factor, threshold_std_devs, partials, npart, vec, st);
+}

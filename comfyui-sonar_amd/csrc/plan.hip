@@ -128,6 +128,8 @@ const Replayable kReplayable[] = {
     SONAR_REPLAYABLE(sonar_dft_rows_c2r_f32),
     SONAR_REPLAYABLE(sonar_perlin_terms_f32),
     SONAR_REPLAYABLE(sonar_perlin_apply_f32),
+    SONAR_REPLAYABLE(sonar_noise_params_scan),
+    SONAR_REPLAYABLE(sonar_noise_params_apply),
 };
 #undef SONAR_REPLAYABLE
 constexpr int kReplayableCount = (int)(sizeof(kReplayable) / sizeof(kReplayable[0]));

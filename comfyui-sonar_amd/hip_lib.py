@@ -193,6 +193,9 @@ SIGNATURES = {
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
     "sonar_cfg_op_prepare": (_I, [_I, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _P]),
     "sonar_cfg_op_finish": (_I, [_I, _P, _P, _P, _P, _I64, _P, _I, _F, _P, _I64, _I64, _P]),
+    "sonar_noise_params_ws_doubles": (_I64, []),
+    "sonar_noise_params_scan": (_I, [_I, _P, _I64, _I64, _I64, _I, _P, _P]),
+    "sonar_noise_params_apply": (_I, [_I, _P, _I, _P, _I64, _I64, _I64, _I, _I, _F, _F, _P, _P]),
     "sonar_axis_taps_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _I, _P]),
     "sonar_axis_taps_f64": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _I, _I, _P]),
     "sonar_dtcwt_q2c_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
@@ -1751,6 +1754,31 @@ def image_rescale_(image: torch.Tensor, part_min: torch.Tensor, part_max: torch.
     return image
 
 
+def noise_params_tail(src: torch.Tensor, out_shape, out_dtype, planes: int, plane_in: int, plane_out: int, *, fix_invalid: bool, normalized: bool,
+                      factor: float, threshold_std_devs: float = 2.5) -> torch.Tensor:
+    """The tail of CustomNoiseParametersNoise (csrc/noise_params.hip): ``src`` is ``planes`` planes of ``plane_in`` values (fp32 / fp16 /
+    bf16), the first ``plane_out`` of each are kept; fix_invalid -> crop -> ``out_dtype`` -> scale_noise(factor, normalized), as a scan
+    launch (skipped when neither flag is set) and an apply launch.  Returns a new tensor of ``out_shape``."""
+    if src.dtype not in DTYPE_IDS or out_dtype not in DTYPE_IDS:
+        raise SonarHipError(f"noise_params_tail: float32 / float16 / bfloat16 only (got {src.dtype} -> {out_dtype})")
+    if planes * plane_in != src.numel() or not 0 < plane_out <= plane_in:
+        raise SonarHipError(f"noise_params_tail: {planes} planes of {plane_in} (kept: {plane_out}) do not describe {src.numel()} values")
+    out = torch.empty(out_shape, dtype=out_dtype, device=src.device)
+    if out.numel() != planes * plane_out:
+        raise SonarHipError(f"noise_params_tail: an output of shape {tuple(out_shape)} does not hold {planes} x {plane_out} values")
+    lib = load()
+    sp, op = _dev(src, "src", src.dtype), _dev(out, "out", out_dtype)
+    partials = None
+    if fix_invalid or normalized:
+        partials = torch.empty(lib.sonar_noise_params_ws_doubles(), dtype=torch.float64, device=src.device)
+        _check(lib.sonar_noise_params_scan(DTYPE_IDS[src.dtype], sp, planes, plane_in, plane_out, int(bool(fix_invalid)),
+                                           _dev(partials, "partials", torch.float64), _stream()), "sonar_noise_params_scan")
+    _check(lib.sonar_noise_params_apply(DTYPE_IDS[src.dtype], sp, DTYPE_IDS[out_dtype], op, planes, plane_in, plane_out, int(bool(fix_invalid)),
+                                        int(bool(normalized)), float(factor), float(threshold_std_devs), _opt(partials, "partials", torch.float64),
+                                        _stream()), "sonar_noise_params_apply")
+    return out
+
+
 def signed_rescale(x: torch.Tensor, rows: int, inner: int, min_neg: float, max_neg: float, min_pos: float, max_pos: float, eps: float = 1e-07) -> torch.Tensor:
     """normalize_to_scale_adv per row of ``inner`` elements (``sonar_signed_rescale_f32``)."""
     out = torch.empty_like(x)
@@ -1846,7 +1874,7 @@ PYRAMID_AHEAD = os.environ.get("SONAR_PYRAMID_AHEAD", "1") != "0"  # plans run a
 PERLIN_AHEAD = os.environ.get("SONAR_PERLIN_AHEAD", "1") != "0"  # plans fuse a normalised Perlin call's three launches (_PerlinAheadHook)
 NOT_RUN = object()      # Plan.run: the step was not issued (a guard changed, an entry point refused): take the ordinary path
 _M64 = 2**64 - 1
-_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_dwt_out_len",
+_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_dwt_out_len",
                            "sonar_dwt2_ws_bytes", "sonar_wcfg_lowpass_lds_bytes", "sonar_wcfg_fused_ws_bytes", "sonar_pyramid_levels",
                            "sonar_plan_fn_id", "sonar_plan_fn_nargs"))
 PATCH_SLOT, PATCH_STREAM, PATCH_SEED, PATCH_BLOB, PATCH_LEVELS = range(5)

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import abc
 import math
+import random
 from functools import partial
 from typing import Callable, Optional
 
@@ -738,6 +739,168 @@ class QuantileFilteredNoise(CustomNoiseItemBase):
             noise = noise_filter(ns(sigma, sigma_next))
             return scale_noise(noise.contiguous(), factor, normalized=normalize)
 
+        return noise_sampler
+
+
+class RNGStates:
+    """py/utils.py:736-791: a snapshot of Python's ``random``, torch's CPU generator and the current device's default generator, which
+    can be put back (``set_states``) and taken again (``update``).  The device generator is captured as (seed, Philox offset): generate
+    mode's values are a function of exactly that pair (``DeviceRNG``), so putting a snapshot back leaves the generator at the offset it
+    had.  Without a device (host-only use) the snapshot holds the two host generators."""
+
+    def __init__(self, device_type=None):
+        self.device_type = device_type
+        self.rng_states = self.get_states()
+
+    @staticmethod
+    def device_generator():
+        if not torch.cuda.is_available():
+            return None
+        # current_device() initialises the runtime if nobody has yet (as DeviceRNG.take does): a snapshot taken before the first device
+        # call must hold the device generator too, or a "separate" item would neither install its seeded position nor restore the caller's
+        return torch.cuda.default_generators[torch.cuda.current_device()]
+
+    @classmethod
+    def get_states(cls) -> dict:
+        states = {"python": random.getstate(), "cpu": torch.get_rng_state()}
+        gen = cls.device_generator()
+        if gen is not None:
+            states["device"] = (torch.cuda.current_device(), gen.initial_seed(), gen.get_offset())
+        return states
+
+    def update(self):
+        self.rng_states = self.get_states()
+
+    def set_states(self):
+        states = self.rng_states
+        random.setstate(states["python"])
+        torch.set_rng_state(states["cpu"].clone())
+        dev = states.get("device")
+        if dev is not None:
+            index, seed, offset = dev
+            gen = torch.cuda.default_generators[index]
+            gen.manual_seed(seed)  # (also puts the offset at 0)
+            gen.set_offset(offset)
+
+
+_PARAMETER_DTYPES = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}
+
+
+class CustomNoiseParametersNoise(CustomNoiseItemBase):
+    """py/noise.py:2080-2187: the wrapped chain with its seed, RNG, layout and dtype arranged, and its output repaired.  What follows the
+    inner sampler -- fix_invalid, the crop back from a squared plane, the conversion to the latent's dtype, scale_noise -- is two launches
+    (csrc/noise_params.hip), or the existing scale_noise alone when there is nothing to fix, crop or convert.  Differences from the
+    reference: ``override_device`` "cpu" selects replay mode and anything else generate mode, the latent stays on
+    the device either way; ``override_dtype`` is float32, float16 or bfloat16."""
+
+    def __init__(self, factor, *, noise, override_dtype=None, override_device=None, **kwargs):
+        super().__init__(factor, noise=noise, override_dtype=self.resolve_dtype(override_dtype), override_device=override_device, **kwargs)
+
+    @staticmethod
+    def resolve_dtype(dtype):
+        """None ("default"), or one of the three dtypes the kernels read and write; NotImplementedError for any other."""
+        if dtype is None or dtype == "default":
+            return None
+        name = dtype if isinstance(dtype, str) else str(dtype).rsplit(".", 1)[-1]
+        if name not in _PARAMETER_DTYPES:
+            raise NotImplementedError(f"SonarCustomNoiseParameters: override_dtype {name} is not supported by this build (the generators "
+                                      "compute in float32 and the tail kernels read and write float32, float16 and bfloat16)")
+        return _PARAMETER_DTYPES[name]
+
+    def clone_key(self, k):
+        if k == "noise":
+            return self.noise.clone()
+        return super().clone_key(k)
+
+    @staticmethod
+    def square_side(x):
+        """(spatial dims, height, width, side of the square plane or None when height * width is a square already) (:2109-2119)."""
+        if x.ndim == 3:
+            spatdims, height, width = 1, 1, x.shape[-1]
+        else:
+            spatdims = 2
+            height, width = x.shape[-2:]
+        hw = (height * width) ** 0.5
+        return spatdims, height, width, (None if hw.is_integer() else math.ceil(hw))
+
+    def make_noise_sampler(self, x, sigma_min=None, sigma_max=None, *args, normalized=True, **kwargs):
+        factor = self.factor
+        normalize = self.get_normalize("normalize", normalized)
+        orig_shape, orig_dtype = x.shape, x.dtype
+        if self.override_device is not None:
+            kwargs["cpu"] = self.override_device == "cpu"
+        if x.ndim == 5 and self.frames_to_channels:
+            x = x.reshape(x.shape[0], x.shape[1] * x.shape[2], *x.shape[3:])
+        fix_invalid = bool(self.fix_invalid)
+        if self.override_dtype is not None and x.dtype != self.override_dtype:
+            x = x.to(dtype=self.override_dtype)
+        plane_out = plane_in = None
+        if self.ensure_square_aspect_ratio:
+            spatdims, height, width, side = self.square_side(x)
+            if side is not None:
+                plane_out, plane_in = height * width, side * side
+                temp_x = x.new_zeros(*x.shape[:-spatdims], plane_in)
+                temp_x[..., :plane_out] = x.flatten(start_dim=-spatdims)
+                x = temp_x.reshape(*temp_x.shape[:-1], side, side)
+        if self.rng_offset_mode in {"override", "add"}:
+            seed = self.rng_state_offset if self.rng_offset_mode == "override" else kwargs.pop("seed", 0) + self.rng_state_offset
+            kwargs["seed"] = seed
+        else:
+            seed = kwargs.get("seed", 0)
+        rng_mode = self.rng_mode
+        rng_state = None
+        if rng_mode == "separate":
+            rng_state = RNGStates(x.device.type)
+            if self.rng_offset_mode != "disabled":
+                caller = rng_state
+                try:
+                    random.seed(seed)
+                    torch.manual_seed(seed)
+                    rng_state = RNGStates(x.device.type)
+                finally:
+                    caller.set_states()
+        ns = self.noise.make_noise_sampler(x, *args, sigma_min=sigma_min, sigma_max=sigma_max, normalized=False, **kwargs)
+        device_type = x.device.type
+
+        def draw(sigma, sigma_next):
+            if rng_mode == "default":
+                return ns(sigma, sigma_next)
+            caller = RNGStates(device_type)
+            try:
+                if rng_mode == "separate":
+                    rng_state.set_states()
+                noise = ns(sigma, sigma_next)
+                if rng_mode == "separate":
+                    rng_state.update()
+            finally:
+                caller.set_states()
+            return noise
+
+        def noise_sampler(sigma, sigma_next):
+            noise = draw(sigma, sigma_next)
+            n = noise.numel()
+            if n == 0:  # nothing to fix or normalise; the latent's own shape and dtype (the inner shape may be folded or squared)
+                return noise.reshape(orig_shape).to(orig_dtype)
+            if not fix_invalid and plane_in is None and noise.dtype == orig_dtype:
+                # nothing to fix, crop or convert: the existing scale_noise (an inner item's look-ahead statistics are consumed by it)
+                if noise.shape != orig_shape:
+                    noise = utils.attach_stats(noise.reshape(orig_shape), pop_stats(noise))
+                if (not normalize and factor == 1) or (noise.dtype == torch.float32 and noise.is_contiguous()):
+                    return scale_noise(noise, factor, normalized=normalize)
+            pop_stats(noise)
+            src = noise if noise.is_contiguous() else noise.contiguous()
+            if plane_in is None:
+                planes, p_in, p_out = 1, n, n
+            else:
+                if n % plane_in:
+                    raise hip_lib.SonarHipError(f"CustomNoiseParametersNoise: the inner sampler returned {tuple(noise.shape)}, not planes of {plane_in}")
+                planes, p_in, p_out = n // plane_in, plane_in, plane_out
+            return hip_lib.noise_params_tail(src, orig_shape, orig_dtype, planes, p_in, p_out, fix_invalid=fix_invalid,
+                                             normalized=bool(normalize), factor=factor)
+
+        if rng_mode == "default" and getattr(ns, "plan_static", False):
+            # the inner step is replayable and the tail is two replayable entry points: a chain holding this item may still be traced
+            noise_sampler.plan_static = True
         return noise_sampler
 
 

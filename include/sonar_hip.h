@@ -319,6 +319,33 @@ int sonar_cfg_op_prepare(int dtype, const void* x, const void* t1, const void* t
 int sonar_cfg_op_finish(int dtype, const float* result, const float* t2, const void* x, const float* sigma, int64_t sigma_n,
                         const void* t1_orig, int blend_mode, float w, void* out, int64_t n, int64_t inner, void* stream);
 
+/* ---------------------------------------------------------------- SonarCustomNoiseParameters */
+/* The tail of CustomNoiseParametersNoise (py/noise.py:2172-2185): fix_invalid, the crop back from a squared plane, the conversion to the
+ * latent's dtype and scale_noise, as two launches without a host synchronisation.  src is `planes` planes of plane_in values of src_dtype
+ * (SONAR_DTYPE_*), of which the first plane_out of each are kept; out is planes * plane_out values of dst_dtype.  Arithmetic is fp32,
+ * statistics are fp64, the result is rounded once (to nearest even).
+ *  sonar_noise_params_scan   one sweep over src -> partials ([SONAR_NOISE_PARAMS_NPART][SONAR_NOISE_PARAMS_SLOT] doubles; only the slots of
+ *                            the launch's blocks are written, and the apply launch of the SAME src / planes / plane_in / plane_out /
+ *                            fix_invalid reads exactly those).  fix_invalid != 0: finite maximum and minimum over ALL values (padding
+ *                            included; two floats in one word), and over the kept values the sum and sum of squares of the finite ones
+ *                            and the counts of +inf, -inf and NaN.  fix_invalid == 0: sum and sum of squares of the kept values as they are.
+ *  sonar_noise_params_apply  per kept value, in this order: with fix_invalid NaN -> 0, +inf -> max(finite maximum, 0), -inf ->
+ *                            min(finite minimum, 0) (nan_to_num_'s extremes are those of the tensor whose non-finite values are 0
+ *                            already); with normalized the two thresholded corrections of scale_noise (mean and unbiased std of the
+ *                            fixed, kept values, derived from the partials; the mean is subtracted as two floats, high part then low
+ *                            part); * factor when factor != 1; written at p * plane_out + i.
+ *                            partials may be NULL when both flags are 0 (a crop / conversion / multiply alone).  out must not be src.
+ * Both plane lengths multiples of 4 and 16-byte aligned buffers: 4 values per lane and access; anything else: one value, per launch.
+ * SONAR_ERR_ARG: an unknown dtype, planes < 0, plane_out <= 0 or > plane_in, more than 2^31 tiles, for planes > 0 a required pointer NULL.
+ * planes == 0 launches nothing. */
+#define SONAR_NOISE_PARAMS_NPART 1024
+#define SONAR_NOISE_PARAMS_SLOT 6
+int64_t sonar_noise_params_ws_doubles(void); /* doubles the partials buffer of the two entry points below must hold */
+int sonar_noise_params_scan(int src_dtype, const void* src, int64_t planes, int64_t plane_in, int64_t plane_out, int fix_invalid,
+                            double* partials, void* stream);
+int sonar_noise_params_apply(int src_dtype, const void* src, int dst_dtype, void* out, int64_t planes, int64_t plane_in, int64_t plane_out,
+                             int fix_invalid, int normalized, float factor, float threshold_std_devs, const double* partials, void* stream);
+
 /* A pending global normalisation of a noise tensor (py/utils.py:100-105): the decision scale_noise(normalized=True) would take,
  * computed ON THE DEVICE from the tensor's (sum, sumsq) partials and left in device memory, so that the kernel that consumes the
  * noise (the sampler-step kernels below take it as `noise_norm`, nullable) applies `((v - mean) / std) * factor` -- only the parts
