@@ -134,12 +134,13 @@ struct QRow {
     int n;       // row length (< 2^31)
     int nslots;  // slots j < nslots of this thread hold values of the row (the same test for every slot: no per-slot masks)
     bool vec;    // float4 layout: slot j of a thread is element ((j / 4) * THREADS + tid) * 4 + j % 4; else j * THREADS + tid
+                 // (one layout for the loads and for map_store: both the row and its destination must allow 16-byte accesses)
     float v[VPT > 0 ? VPT : 1];
 
-    __device__ __forceinline__ void load(const float* r, int len) {
+    __device__ __forceinline__ void load(const float* r, int len, const float* dst) {
         row = r;
         n = len;
-        vec = (reinterpret_cast<uintptr_t>(r) & 15u) == 0 && (len & 3) == 0;
+        vec = ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0 && (len & 3) == 0;  // (dst may be null)
         const int tid = threadIdx.x;
         nslots = vec ? 4 * (((len >> 2) - tid + THREADS - 1) / THREADS) : (len - tid + THREADS - 1) / THREADS;
         if constexpr (VPT > 0) {
@@ -286,7 +287,7 @@ __global__ void __launch_bounds__(THREADS) quantile_rows_kernel(QRowArgs a) {
     const int base = a.op & 0xFF;
     for (int64_t r = blockIdx.x; r < a.rows; r += gridDim.x) {
         QRow<THREADS, VPT> row;
-        row.load(a.x + r * a.inner, (int)a.inner);
+        row.load(a.x + r * a.inner, (int)a.inner, a.out ? a.out + r * a.inner : nullptr);
         auto fmax_ = [](float p, float q) { return fmaxf(p, q); };
         float mx = 0.0f;
         row.each([&](float x) { mx = fmaxf(mx, fabsf(x)); });

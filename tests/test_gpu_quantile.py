@@ -1,6 +1,6 @@
 """GPU: utils.quantile_normalize (HIP radix select + strategy kernels) against the reference's outputs and refusals
-(tests/golden/quantile_filter.npz, tests/golden/make_quantile_golden.py), and against a float64 CPU restatement on large shapes: the
-register-resident rows, the re-read long rows, dim 0 and "global"."""
+(tests/golden/quantile_filter.npz, tests/golden/make_quantile_golden.py), and against a float64 CPU restatement (tests/quantile_refs.py)
+on large shapes: the register-resident rows, the re-read long rows, dim 0 and "global"."""
 import importlib
 import json
 import zlib
@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests.conftest import GOLDEN
+from tests.quantile_refs import _restated
 
 pytestmark = pytest.mark.gpu
 
@@ -54,60 +55,6 @@ def test_reference_cases(pkg, name):
 
 
 # ------------------------------------------------------------------------------------------------ beyond the reference
-def _rows(x, dim, flatten):
-    """(rows [R, L] float32, function putting [R, L] back into x's shape, row of every element in memory order)."""
-    if dim is None:
-        return x.reshape(1, -1), lambda r: r.reshape(x.shape)
-    if flatten:
-        return x.reshape(int(np.prod(x.shape[:dim])), -1), lambda r: r.reshape(x.shape)
-    xt = x.movedim(dim, -1)
-    shape_t = xt.shape
-    return xt.reshape(-1, x.shape[dim]), lambda r: r.reshape(shape_t).movedim(-1, dim)
-
-
-def _restated(x, q, dim, flatten, strategy, pow_fac=0.5, nq_fac=1.0, eps=1e-8):
-    """float64 restatement: per-row sort for the order statistics (no torch.quantile), fp32 rank and threshold as the reference forms them."""
-    rows, back = _rows(x, dim, flatten)
-    centered = q < 0
-    maxabs = rows.abs().amax(dim=1, keepdim=True)
-    p = rows.sign() * (maxabs - rows.abs()) if centered else rows
-    srt = p.abs().sort(dim=1).values
-    n = rows.shape[1]
-    rank = torch.tensor(abs(q), dtype=torch.float32) * (n - 1)
-    lo = int(torch.floor(rank))
-    frac = (rank - lo).reshape(1, 1)
-    nq = torch.lerp(srt[:, lo:lo + 1], srt[:, min(lo + 1, n - 1):min(lo + 1, n - 1) + 1], frac.expand(rows.shape[0], 1))
-    nq = nq * torch.tensor(nq_fac, dtype=torch.float32) + torch.tensor(eps, dtype=torch.float32)
-    p64, nq64 = p.double(), nq.double()
-    outl = p.abs() > nq
-    if strategy == "clamp":
-        o = torch.minimum(torch.maximum(p64, -nq64), nq64)
-    elif strategy == "median":
-        med = p.sort(dim=1).values[:, (n - 1) // 2:(n - 1) // 2 + 1].double()
-        o = torch.where(outl, med, p64)
-    elif strategy == "mode_2dec":
-        o = torch.where(outl, torch.round(p, decimals=2).mode(dim=1, keepdim=True).values.double(), p64)
-    elif strategy == "mean":
-        o = torch.where(outl, p64.mean(dim=1, keepdim=True), p64)
-    elif strategy == "scale_down":
-        mv = p.abs().amax(dim=1, keepdim=True).clamp(min=1e-6).double()
-        o = torch.where(outl, p64 * (nq64 / mv), p64)
-    elif strategy == "replace_2pt":
-        pf = back(p).reshape(-1)
-        mask = back(~outl).reshape(-1)
-        cand = pf[mask].double()
-        idx = torch.arange(pf.numel()) % cand.numel()
-        rep = cand[idx] * 0.5 + cand[torch.roll(idx, 1)] * 0.5
-        o = torch.where(mask, pf.double(), rep)
-        o = _rows(o.reshape(x.shape), dim, flatten)[0]
-    else:
-        raise AssertionError(strategy)
-    if centered:
-        o = o.sign() * (maxabs.double() - o.abs())
-    o = o.abs().pow(pow_fac).copysign(o)
-    return back(o)
-
-
 BIG = [((64, 4, 128, 128), 1, True, "resident rows of 65536"), ((2, 16, 128, 128), 1, True, "a 256 Ki row"),
        ((4, 4, 128, 128), 1, True, "few resident rows"), ((3, 2, 64, 64), 1, False, "short rows along a middle dim"),
        ((8, 4, 128, 128), 0, True, "dim 0: one row of 512 Ki"), ((2, 4, 64, 64), None, False, "global")]
