@@ -408,6 +408,20 @@ __device__ __forceinline__ T blend(int mode, T a, T b, T t) {
     return a - b * t;
 }
 
+// ---- per-row / per-group updates (elementwise.hip's row kernels and group_stats.hip's strided ones share the arithmetic) ------------
+// sonar_row_affine_f32: op 0 (x - a) / b, op 1 x * b + a
+__device__ __forceinline__ float row_affine_value(int op, float x, float a, float b) { return op == 0 ? (x - a) / b : x * b + a; }
+
+// normalize_to_scale's tail (py/utils.py:462-469): ((x - lo) / ((hi - lo) + eps)) * (tmax - tmin) + tmin, clamped; each step rounded
+// on its own as the reference's in-place tensor ops are.  The targets are Python floats there: their difference is formed in double
+// and rounded to fp32 ONCE (`span`; 0.3 - 0.1 is 0.2, not 0.20000002)
+__device__ __forceinline__ float minmax_rescale_value(float x, float lo, float hi, float eps, float tmin, float tmax, float span) {
+    const float denom = __fadd_rn(__fsub_rn(hi, lo), eps);
+    float v = __fsub_rn(x, lo) / denom;
+    v = __fadd_rn(__fmul_rn(v, span), tmin);
+    return v != v ? v : fminf(fmaxf(v, tmin), tmax);  // clamp_ keeps NaN
+}
+
 }  // namespace sonar
 
 // power_fft.hip (power_any.h): the LDS line transforms as passes through a complex workspace, for the planes beyond LDS; false = not

@@ -407,13 +407,11 @@ __global__ void __launch_bounds__(kBlock) row_affine_kernel(int op, const float*
     const int64_t total = rows * inner;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
         const int64_t r = i / inner;
-        out[i] = op == 0 ? (x[i] - a[r]) / b[r] : x[i] * b[r] + a[r];
+        out[i] = row_affine_value(op, x[i], a[r], b[r]);
     }
 }
 
-// normalize_to_scale's tail (py/utils.py:462-469): ((x - lo) / ((hi - lo) + eps)) * (tmax - tmin) + tmin, clamped; each step rounded
-// on its own as the reference's in-place tensor ops are.  The targets are Python floats there: their difference is formed in double
-// and rounded to fp32 ONCE (`span`; 0.3 - 0.1 is 0.2, not 0.20000002)
+// normalize_to_scale's tail (py/utils.py:462-469) per row: minmax_rescale_value (common.h)
 __global__ void __launch_bounds__(kBlock) minmax_rescale_kernel(const float* __restrict__ x, int64_t rows, int64_t inner,
                                                                  const float* __restrict__ lo, const float* __restrict__ hi, float eps,
                                                                  float tmin, float tmax, float span, float* out) {
@@ -421,10 +419,7 @@ __global__ void __launch_bounds__(kBlock) minmax_rescale_kernel(const float* __r
     const int64_t total = rows * inner;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
         const int64_t r = i / inner;
-        const float denom = __fadd_rn(__fsub_rn(hi[r], lo[r]), eps);
-        float v = __fsub_rn(x[i], lo[r]) / denom;
-        v = __fadd_rn(__fmul_rn(v, span), tmin);
-        out[i] = v != v ? v : fminf(fmaxf(v, tmin), tmax);  // clamp_ keeps NaN
+        out[i] = minmax_rescale_value(x[i], lo[r], hi[r], eps, tmin, tmax, span);
     }
 }
 

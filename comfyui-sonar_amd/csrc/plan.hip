@@ -130,6 +130,10 @@ const Replayable kReplayable[] = {
     SONAR_REPLAYABLE(sonar_perlin_apply_f32),
     SONAR_REPLAYABLE(sonar_noise_params_scan),
     SONAR_REPLAYABLE(sonar_noise_params_apply),
+    SONAR_REPLAYABLE(sonar_group_stats_f32),
+    SONAR_REPLAYABLE(sonar_group_affine_f32),
+    SONAR_REPLAYABLE(sonar_group_minmax_rescale_f32),
+    SONAR_REPLAYABLE(sonar_group_adjust_f32),
 };
 #undef SONAR_REPLAYABLE
 constexpr int kReplayableCount = (int)(sizeof(kReplayable) / sizeof(kReplayable[0]));

@@ -188,6 +188,11 @@ SIGNATURES = {
     "sonar_wcfg_bands_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _PD, _PD, _PD, _PD, _I, _I, _I, _PD, _D, _D, _D, _I, _P]),
     "sonar_wcfg_bands_f64": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _PD, _PD, _PD, _PD, _I, _I, _I, _PD, _D, _D, _D, _I, _P]),
     "sonar_minmax_rescale_f32": (_I, [_P, _I64, _I64, _P, _P, _F, _D, _D, _P, _P]),
+    "sonar_group_stats_ws_doubles": (_I64, [_I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I, _I]),
+    "sonar_group_stats_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "sonar_group_affine_f32": (_I, [_I, _P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "sonar_group_minmax_rescale_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _F, _D, _D, _P, _P]),
+    "sonar_group_adjust_f32": (_I, [_I, _P, _I64, _F, _P, _P]),
     "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
@@ -1709,6 +1714,91 @@ def minmax_rescale(x: torch.Tensor, rows: int, inner: int, lo: torch.Tensor, hi:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ statistics over any dimensions
+GROUP_MAX_SEGMENTS = 6  # SONAR_GROUP_MAX_SEGMENTS
+
+
+def check_dims(ndim: int, dims) -> tuple:
+    """``dims`` as non-negative dimensions of an ``ndim``-dimensional tensor, refused as torch refuses a ``dim`` tuple: IndexError for a
+    dimension out of range, RuntimeError for one named twice.  An empty tuple stays empty (the caller's "all dimensions")."""
+    out = []
+    span = max(ndim, 1)  # a 0-d tensor takes -1 and 0, as torch's does
+    for d in dims:
+        d = int(d)
+        if not -span <= d < span:
+            raise IndexError(f"Dimension out of range (expected to be in range of [{-span}, {span - 1}], but got {d})")
+        d %= span
+        if d in out:
+            raise RuntimeError(f"dim {d} appears multiple times in the list of dims")
+        out.append(d)
+    return tuple(out)
+
+
+def group_segments(shape, dims):
+    """(segment sizes outermost first, first_reduced, groups) of a reduction of a contiguous tensor of ``shape`` over ``dims`` (empty: every
+    dimension): adjacent dimensions of one kind merged, size-1 dimensions dropped, so the segments alternate between reduced and kept."""
+    shape = tuple(int(n) for n in shape)
+    reduced = set(check_dims(len(shape), dims)) if len(dims) else set(range(len(shape)))
+    segs = []  # [size, reduced]
+    for d, n in enumerate(shape):
+        if n == 1:
+            continue
+        if segs and segs[-1][1] == (d in reduced):
+            segs[-1][0] *= n
+        else:
+            segs.append([n, d in reduced])
+    if not segs:
+        segs = [[1, False]]  # one element: one group of one member
+    if len(segs) > GROUP_MAX_SEGMENTS:
+        raise SonarHipError(f"a reduction over dims {tuple(dims)} of shape {shape} alternates {len(segs)} times; the kernels take {GROUP_MAX_SEGMENTS} segments")
+    return [n for n, _r in segs], int(segs[0][1]), math.prod(n for n, r in segs if not r)
+
+
+def _segment_args(shape, dims):
+    sizes, first, groups = group_segments(shape, dims)
+    return (len(sizes), first, *sizes, *([1] * (GROUP_MAX_SEGMENTS - len(sizes)))), groups
+
+
+def group_stats(x: torch.Tensor, dims, *, mean_std: bool = True, minmax: bool = False):
+    """Per group of ``x`` over ``dims`` (``group_segments``), as flat tensors in the keepdim=True order: (mean, unbiased std) and / or (min, max),
+    in one sweep over ``x`` as it lies (csrc/group_stats.hip)."""
+    seg, groups = _segment_args(x.shape, dims)
+    lib = load()
+    res = [torch.empty(groups, dtype=torch.float32, device=x.device) for _ in range(2 * (bool(mean_std) + bool(minmax)))]
+    need = lib.sonar_group_stats_ws_doubles(*seg, int(bool(mean_std)), int(bool(minmax)))
+    if need < 0:
+        _check(need, "sonar_group_stats_ws_doubles")
+    ws = torch.empty(need, dtype=torch.float64, device=x.device) if need else None
+    ptrs = [_dev(t, "result") for t in res]
+    ms, mm = (ptrs[:2] if mean_std else [None, None]), (ptrs[-2:] if minmax else [None, None])
+    _check(lib.sonar_group_stats_f32(_dev(x, "x"), *seg, *ms, *mm, _opt(ws, "ws", torch.float64), _stream()), "sonar_group_stats_f32")
+    return tuple(res)
+
+
+def group_affine(op: int, x: torch.Tensor, dims, a: Optional[torch.Tensor], b: Optional[torch.Tensor]) -> torch.Tensor:
+    """``row_affine`` with the operands of the element's group over ``dims``; ``a`` None is 0, ``b`` None is 1."""
+    seg, _groups = _segment_args(x.shape, dims)
+    out = torch.empty_like(x)
+    _check(load().sonar_group_affine_f32(op, _dev(x, "x"), *seg, _opt(a, "a"), _opt(b, "b"), _dev(out, "out"), _stream()), "sonar_group_affine_f32")
+    return out
+
+
+def group_minmax_rescale(x: torch.Tensor, dims, lo: torch.Tensor, hi: torch.Tensor, eps: float, target_min: float, target_max: float) -> torch.Tensor:
+    """``minmax_rescale`` with the (lo, hi) of the element's group over ``dims``."""
+    seg, _groups = _segment_args(x.shape, dims)
+    out = torch.empty_like(x)
+    _check(load().sonar_group_minmax_rescale_f32(_dev(x, "x"), *seg, _dev(lo, "lo"), _dev(hi, "hi"), float(eps), float(target_min),
+                                                 float(target_max), _dev(out, "out"), _stream()), "sonar_group_minmax_rescale_f32")
+    return out
+
+
+def group_adjust(op: int, v: torch.Tensor, k: float) -> torch.Tensor:
+    """NormalizeToScaleNoise's per-group scalars: op 0 ``v * k``; op 1 ``t = (v - 1) * k + 1`` with 1e-07 where t == 0."""
+    out = torch.empty_like(v)
+    _check(load().sonar_group_adjust_f32(op, _dev(v, "v"), v.numel(), float(k), _dev(out, "out"), _stream()), "sonar_group_adjust_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ SonarNoiseImage
 IMAGE_BLEND_IDS = BLEND_IDS | {"simple_add": 3}  # SONAR_IMAGE_BLEND_ADD
 IMAGE_NPART, IMAGE_MAX_CHANNELS = 1024, 64       # SONAR_IMAGE_NPART, SONAR_IMAGE_MAX_CHANNELS
@@ -1874,7 +1964,7 @@ PYRAMID_AHEAD = os.environ.get("SONAR_PYRAMID_AHEAD", "1") != "0"  # plans run a
 PERLIN_AHEAD = os.environ.get("SONAR_PERLIN_AHEAD", "1") != "0"  # plans fuse a normalised Perlin call's three launches (_PerlinAheadHook)
 NOT_RUN = object()      # Plan.run: the step was not issued (a guard changed, an entry point refused): take the ordinary path
 _M64 = 2**64 - 1
-_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_dwt_out_len",
+_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_dwt_out_len",
                            "sonar_dwt2_ws_bytes", "sonar_wcfg_lowpass_lds_bytes", "sonar_wcfg_fused_ws_bytes", "sonar_pyramid_levels",
                            "sonar_plan_fn_id", "sonar_plan_fn_nargs"))
 PATCH_SLOT, PATCH_STREAM, PATCH_SEED, PATCH_BLOB, PATCH_LEVELS = range(5)

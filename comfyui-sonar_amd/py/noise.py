@@ -1028,26 +1028,29 @@ class NormalizeToScaleNoise(CustomNoiseItemBase):
         return self.noise.clone() if k == "noise" else super().clone_key(k)
 
     @staticmethod
-    def _trailing(noise: Tensor, dims, what: str):
-        """(rows, inner) of a reduction over ``dims``, which must be the trailing dimensions (the node's '-3, -2, -1' and its suffixes)."""
-        nd = noise.ndim
-        want = sorted(d % nd for d in dims) if len(dims) else list(range(nd))
-        if want != list(range(nd - len(want), nd)):
-            raise hip_lib.SonarHipError(f"NormalizeToScaleNoise: {what} must be the trailing dimensions on the HIP path (got {tuple(dims)})")
-        inner = math.prod(noise.shape[nd - len(want):])
-        return noise.numel() // max(inner, 1), inner
+    def _trailing(ndim: int, shape, dims):
+        """(rows, inner) when a reduction over ``dims`` (checked, non-negative; empty: all) is one over trailing dimensions -- rows of
+        ``inner`` contiguous elements, the route of ``rowstats`` + ``row_affine`` -- and None for any other choice (``hip_lib.group_stats``)."""
+        want = sorted(dims) if len(dims) else list(range(ndim))
+        if want != list(range(ndim - len(want), ndim)):
+            return None
+        inner = math.prod(shape[ndim - len(want):])
+        return math.prod(shape) // max(inner, 1), inner
 
     def make_noise_sampler(self, x, *args, normalized=True, **kwargs):
-        std_dims, std_multiplier = self.std_dims, self.std_multiplier
-        mean_dims, mean_multiplier = self.mean_dims, self.mean_multiplier
+        std_multiplier, mean_multiplier = self.std_multiplier, self.mean_multiplier
         factor, mode = self.factor, self.mode
+        # what torch.mean / torch.std refuse (a dimension out of range: IndexError, one named twice: RuntimeError) is refused here, with
+        # torch's exception types, before anything is launched (the reference meets them at its first call)
+        mean_dims = hip_lib.check_dims(x.ndim, self.mean_dims) if mean_multiplier != 0 else ()
+        std_dims = hip_lib.check_dims(x.ndim, self.std_dims) if std_multiplier != 0 else ()
         ns = self.noise.make_noise_sampler(x, *args, normalized=self.normalize_noise, **kwargs)
         normalize = self.get_normalize("normalize", normalized)
 
         def noise_sampler(s, sn):
             noise = ns(s, sn)
             pop_stats(noise)
-            noise = utils.as_f32(noise).contiguous()
+            noise = utils.as_f32(noise)  # (contiguous)
             if mode == "simple":
                 noise = utils.normalize_to_scale(noise, self.min_negative_value, self.max_positive_value, dim=self.dims)
             else:
@@ -1055,18 +1058,34 @@ class NormalizeToScaleNoise(CustomNoiseItemBase):
                 rows = 1 if (noise.ndim < 2 or not self.dims) else noise.shape[0]
                 noise = hip_lib.signed_rescale(noise, rows, noise.numel() // max(rows, 1), self.min_negative_value, self.max_negative_value,
                                                self.min_positive_value, self.max_positive_value)
-            if mean_multiplier != 0:
-                rows, inner = self._trailing(noise, mean_dims, "mean_dims")
-                mean, _ = hip_lib.rowstats(noise, rows, inner)
-                noise = hip_lib.row_affine(0, noise, rows, inner, mean * mean_multiplier, torch.ones_like(mean))  # (x - m k) / 1
-            if std_multiplier != 0:
-                rows, inner = self._trailing(noise, std_dims, "std_dims")
-                _, std = hip_lib.rowstats(noise, rows, inner)
-                adj = (std - 1.0) * std_multiplier + 1.0
-                adj = torch.where(adj == 0, torch.full_like(adj, 1e-07), adj)
-                noise = hip_lib.row_affine(0, noise, rows, inner, torch.zeros_like(adj), adj)
+            if mean_multiplier != 0 and noise.numel():
+                rows_inner = self._trailing(noise.ndim, noise.shape, mean_dims)
+                if rows_inner is not None:
+                    rows, inner = rows_inner
+                    mean, _ = hip_lib.rowstats(noise, rows, inner)
+                    noise = hip_lib.row_affine(0, noise, rows, inner, mean * mean_multiplier, torch.ones_like(mean))  # (x - m k) / 1
+                else:  # any other dims: strided statistics, entry points only (the step stays replayable)
+                    mean, _ = hip_lib.group_stats(noise, mean_dims)
+                    noise = hip_lib.group_affine(0, noise, mean_dims, hip_lib.group_adjust(0, mean, mean_multiplier), None)
+            if std_multiplier != 0 and noise.numel():
+                rows_inner = self._trailing(noise.ndim, noise.shape, std_dims)
+                if rows_inner is not None:
+                    rows, inner = rows_inner
+                    _, std = hip_lib.rowstats(noise, rows, inner)
+                    adj = (std - 1.0) * std_multiplier + 1.0
+                    adj = torch.where(adj == 0, torch.full_like(adj, 1e-07), adj)
+                    noise = hip_lib.row_affine(0, noise, rows, inner, torch.zeros_like(adj), adj)
+                else:
+                    _, std = hip_lib.group_stats(noise, std_dims)
+                    noise = hip_lib.group_affine(0, noise, std_dims, None, hip_lib.group_adjust(1, std, std_multiplier))
             return scale_noise(noise, factor, normalized=normalize)
 
+        steps = [d for d, k in ((mean_dims, mean_multiplier), (std_dims, std_multiplier)) if k != 0]
+        if (mode == "simple" and getattr(ns, "plan_static", False) and x.dtype == torch.float32
+                and all(self._trailing(x.ndim, x.shape, d) is None for d in steps)):
+            # the inner step is replayable and every launch of this one is a replayable entry point (the trailing route computes its
+            # per-row operands with torch operations, the advanced mode's kernel is not in the set): a chain holding the item may be traced
+            noise_sampler.plan_static = True
         return noise_sampler
 
 

@@ -188,6 +188,11 @@ def normalize_to_scale(latent: Tensor, target_min: float, target_max: float, *, 
     _require_device(latent, "normalize_to_scale")
     x = as_f32(latent)
     dims = sorted({d % x.ndim for d in dim}) if len(dim) else list(range(x.ndim))
+    if dims != list(range(x.ndim - len(dims), x.ndim)):
+        # not the trailing dimensions: min / max and the rescale on the tensor as it lies (csrc/group_stats.hip) -- the same values as the
+        # row kernels give on a transposed copy (min and max do not depend on the order, the rescale is one device function), bit for bit
+        lo, hi = hip_lib.group_stats(x, dims, mean_std=False, minmax=True)
+        return hip_lib.group_minmax_rescale(x, dims, lo, hi, eps, target_min, target_max)
     x, inverse = dims_last(x, dims)
     inner = 1
     for d in range(x.ndim - len(dims), x.ndim):

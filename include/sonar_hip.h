@@ -296,6 +296,35 @@ int sonar_minmax_rows_f32(const float* x, int64_t rows, int64_t inner, float* ou
 int sonar_minmax_rescale_f32(const float* x, int64_t rows, int64_t inner, const float* lo, const float* hi, float eps,
                              double target_min, double target_max, float* out, void* stream);
 
+/* ---------------------------------------------------------------- statistics over any subset of dimensions (csrc/group_stats.hip)
+ * torch.mean / torch.std / amin / amax with dim = any tuple and keepdim = True (NormalizeToScaleNoise, py/noise.py:1287-1296;
+ * normalize_to_scale, py/utils.py:452-470) on the contiguous tensor as it lies.  The caller collapses (shape, reduced dims) into
+ * `nseg` <= SONAR_GROUP_MAX_SEGMENTS alternating segments s0.., outermost first (adjacent dimensions of one kind merged, size-1 dimensions
+ * dropped; the sizes beyond nseg are ignored); segment k is reduced when (k odd) != first_reduced.  A group is one coordinate of the kept
+ * segments, numbered row-major over them: the flattened keepdim layout.
+ *  sonar_group_stats_f32           per group mean and unbiased std (one member: NaN, like torch) and / or min and max; the pair not wanted
+ *                                  is NULL.  fp64 sums of x and x^2 as sonar_rowstats_f32; long reductions over few groups are split over
+ *                                  workgroups, the parts left in `ws` and added in a fixed order by a second launch (same bits every run).
+ *                                  ws: sonar_group_stats_ws_doubles(...) doubles (0: not split, ws may be NULL).
+ *  sonar_group_affine_f32          sonar_row_affine_f32's operations with a[g], b[g] of the element's group; a NULL a is 0, a NULL b is 1
+ *                                  (not both); out may be x
+ *  sonar_group_minmax_rescale_f32  sonar_minmax_rescale_f32's arithmetic with lo[g], hi[g]; out may be x
+ *  sonar_group_adjust_f32          NormalizeToScaleNoise's per-group scalars, n values: op 0 out = v * k; op 1 t = (v - 1) * k + 1,
+ *                                  out = 1e-07 where t == 0 (NaN stays NaN); out may be v
+ * SONAR_ERR_ARG: nseg outside 1..6, a negative size, a required pointer NULL, a result of sonar_group_stats_f32 (or ws) equal to x, an
+ * operand table equal to out, a split shape without ws.  SONAR_ERR_UNSUPPORTED: 2^31 elements or more.  A size of 0 launches nothing. */
+#define SONAR_GROUP_MAX_SEGMENTS 6
+int64_t sonar_group_stats_ws_doubles(int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4, int64_t s5,
+                                     int want_mean_std, int want_min_max);
+int sonar_group_stats_f32(const float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                          int64_t s5, float* mean, float* stdv, float* lo, float* hi, double* ws, void* stream);
+int sonar_group_affine_f32(int op, const float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                           int64_t s5, const float* a, const float* b, float* out, void* stream);
+int sonar_group_minmax_rescale_f32(const float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                                   int64_t s5, const float* lo, const float* hi, float eps, double target_min, double target_max,
+                                   float* out, void* stream);
+int sonar_group_adjust_f32(int op, const float* v, int64_t n, float k, float* out, void* stream);
+
 /* ---------------------------------------------------------------- latent operations under CFG */
 /* SonarApplyLatentOperationCFG (py/nodes/latent_operations.py:246-300): the arithmetic on either side of the latent operations, one launch
  * each.  x, t1, t2, t1_orig and out are n contiguous values of `dtype` (SONAR_DTYPE_*: widened to fp32 at load, `out` rounded once, to
