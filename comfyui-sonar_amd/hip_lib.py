@@ -196,6 +196,8 @@ SIGNATURES = {
     "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
+    "sonar_preview_panels_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _I, _P, _P]),
+    "sonar_preview_compose_u8": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _P, _P]),
     "sonar_cfg_op_prepare": (_I, [_I, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _P]),
     "sonar_cfg_op_finish": (_I, [_I, _P, _P, _P, _P, _I64, _P, _I, _F, _P, _I64, _I64, _P]),
     "sonar_noise_params_ws_doubles": (_I64, []),
@@ -1842,6 +1844,52 @@ def image_rescale_(image: torch.Tensor, part_min: torch.Tensor, part_max: torch.
     _check(load().sonar_image_rescale_f32(_dev(image, "image"), b, c, h * w, _dev(part_min, "part_min"), _dev(part_max, "part_max"),
                                           float(eps), _stream()), "sonar_image_rescale_f32")
     return image
+
+
+# ------------------------------------------------------------------------------------------------ filter previews
+def preview_filter_width(W: int) -> int:
+    """Columns of the filter panel (``rfft2_to_fft2`` of a [H, W/2+1] half-spectrum): the mirrored half drops column 0 always and the last
+    column only for an odd W/2+1 -- 2 Wh - 2 or 2 Wh - 1, not always W (the reference's widths: W = 6 gives 7, W = 9 gives 8)."""
+    wh = int(W) // 2 + 1
+    return 2 * wh - 2 if wh & 1 else 2 * wh - 1
+
+
+def _preview_planes(filt: torch.Tensor, kernel: Optional[torch.Tensor], noise: Optional[torch.Tensor], W: int, what: str):
+    if filt.ndim < 2 or filt.shape[-1] != W // 2 + 1:
+        raise SonarHipError(f"{what}: filter {tuple(filt.shape)} is no [..., H, {W // 2 + 1}] half-spectrum of width {W}")
+    lead, H = tuple(filt.shape[:-2]), int(filt.shape[-2])
+    for name, t in (("kernel", kernel), ("noise", noise)):
+        if t is not None and tuple(t.shape) != (*lead, H, W):
+            raise SonarHipError(f"{what}: {name} {tuple(t.shape)} is not {(*lead, H, W)}")
+    return lead, H
+
+
+def preview_panels(filt: torch.Tensor, kernel: Optional[torch.Tensor], noise: Optional[torch.Tensor], W: int, *, filter_gain: float = 1 / 3,
+                   kernel_gain: float = 1 / 3, gain: bool = True) -> torch.Tensor:
+    """``sonar_preview_panels_f32``: the preview's panels as fp32, [..., H, FW + W (+ W with ``noise``)] for a filter [..., H, W/2+1], its
+    un-rolled irfft2 ``kernel`` [..., H, W] and an optional ``noise`` plane.  ``gain=False`` moves the data only; with ``kernel=None`` (and
+    no noise) the result is ``rfft2_to_fft2(filt)``."""
+    lead, H = _preview_planes(filt, kernel, noise, W, "preview_panels")
+    width = preview_filter_width(W) + (W if kernel is not None else 0) + (W if noise is not None else 0)
+    out = torch.empty((*lead, H, width), dtype=torch.float32, device=filt.device)
+    nh, nw = (H, W) if noise is not None else (0, 0)
+    _check(load().sonar_preview_panels_f32(_dev(filt, "filter"), _opt(kernel, "kernel"), _opt(noise, "noise"), math.prod(lead), H, W, nh, nw,
+                                           float(filter_gain), float(kernel_gain), int(bool(gain)), _dev(out, "out"), _stream()),
+           "sonar_preview_panels_f32")
+    return out
+
+
+def preview_compose(filt: torch.Tensor, kernel: torch.Tensor, noise: Optional[torch.Tensor], W: int, *, filter_gain: float = 1 / 3,
+                    kernel_gain: float = 1 / 3) -> torch.Tensor:
+    """``sonar_preview_compose_u8``: the same panels as grey levels, ``clamp(0, 255)`` truncated to uint8."""
+    lead, H = _preview_planes(filt, kernel, noise, W, "preview_compose")
+    width = preview_filter_width(W) + W + (W if noise is not None else 0)
+    out = torch.empty((*lead, H, width), dtype=torch.uint8, device=filt.device)
+    nh, nw = (H, W) if noise is not None else (0, 0)
+    _check(load().sonar_preview_compose_u8(_dev(filt, "filter"), _opt(kernel, "kernel"), _opt(noise, "noise"), math.prod(lead), H, W, nh, nw,
+                                           float(filter_gain), float(kernel_gain), _dev(out, "out", torch.uint8), _stream()),
+           "sonar_preview_compose_u8")
+    return out
 
 
 def noise_params_tail(src: torch.Tensor, out_shape, out_dtype, planes: int, plane_in: int, plane_out: int, *, fix_invalid: bool, normalized: bool,

@@ -8,7 +8,11 @@ normaliser's statistics (``sonar_power_irfft2_f32``); mixing and normalisation a
 """
 from __future__ import annotations
 
+import importlib
 import math
+import os
+import random
+import tempfile
 
 import torch
 from torch import Tensor
@@ -18,6 +22,58 @@ from ..noise import CustomNoiseItemBase
 from ..noise_generation import BrownianTreeNoiseSampler, DeviceRNG, current_batch_offset
 from .. import utils
 from ..utils import attach_stats, pop_stats, scale_noise
+
+
+def _host_module(name: str):
+    """A ComfyUI host module (``folder_paths``, ``latent_preview``, ``comfy.latent_formats``) when the pack runs inside ComfyUI, None when
+    the module (or a package on the way to it) does not exist.  A module that exists and fails to import raises as it does anywhere."""
+    try:
+        return importlib.import_module(name)
+    except ModuleNotFoundError as exc:
+        if exc.name is not None and (name == exc.name or name.startswith(exc.name + ".")):
+            return None
+        raise  # something the host module itself imports is missing: its failure, not its absence
+
+
+_PREVIEW_NAMES = random.Random()  # file-name suffixes of the preview images: its own generator, the global ``random`` state is the graph's
+
+
+def make_preview_result(img, result, prefix="sonar_temp"):
+    """py/nodes/powernoise.py:33-53: the image saved as a temp PNG and announced to the UI next to the node's ``result``.  Inside ComfyUI
+    the file goes where ``folder_paths`` says; without that module it goes into the system's temp directory."""
+    name = f"{prefix}_" + "".join(_PREVIEW_NAMES.choice("abcdefghijklmnopqrstupvxyz") for _ in range(5))
+    folder_paths = _host_module("folder_paths")
+    if folder_paths is not None:
+        folder, filename, counter, subfolder, _ = folder_paths.get_save_image_path(name, folder_paths.get_temp_directory())
+    else:
+        folder, filename, counter, subfolder = tempfile.gettempdir(), name, 0, ""
+    filename = f"{filename}_{counter:05}_.png"
+    img.save(os.path.join(folder, filename), compress_level=1)
+    return {"ui": {"images": [{"filename": filename, "subfolder": subfolder, "type": "temp"}]}, "result": result}
+
+
+def _preview_device() -> torch.device:
+    if not torch.cuda.is_available():
+        raise hip_lib.SonarHipError("filter previews are composed by a HIP kernel: no ROCm device is available")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _to_image(levels: Tensor):
+    from PIL import Image
+
+    return Image.fromarray(levels[0, 0].cpu().numpy())
+
+
+def rfft2_to_fft2(x: Tensor) -> Tensor:
+    """py/nodes/powernoise.py:457-468: the full spectrum's picture from a real half-spectrum ``[..., H, W/2+1]`` on the device -- rows
+    fft-shifted, the mirrored half (both axes flipped, one more row of roll for an even H, column 0 dropped and the last column too when
+    the half-spectrum's width is odd) on the left.  Data movement only, in the preview kernel's addressing.  Only for previews; real
+    float32 tensors (the filters): a complex one would need its mirrored half conjugated."""
+    if x.is_complex():
+        raise hip_lib.SonarHipError("rfft2_to_fft2: real half-spectra only (the preview's filters)")
+    wh = int(x.shape[-1])
+    # the panel's width depends on the half-spectrum's width alone: any W with W // 2 + 1 == wh addresses the same elements
+    return hip_lib.preview_panels(x.contiguous(), None, None, 2 * (wh - 1), gain=False)
 
 
 class ChannelMixer:
@@ -141,6 +197,30 @@ class PowerFilter:
             return self.compose(gain, self.compose_with.build(shape, override_oversample=override_oversample), self.compose_mode)
         return gain
 
+    def preview(self, size=(128, 128), mix=1.0, normalization_factor=1.0, raw=False, kernel_gain=1 / 3, filter_gain=1 / 3):
+        """py/nodes/powernoise.py:268-294: the filter's spectrum and its spatial kernel side by side.  ``raw``: the two fp32 panels
+        ``[1, 1, H, .]`` (views of one device tensor), else a PIL ``L`` image."""
+        size = tuple(int(v) for v in size)
+        filt, kernel = self._preview_planes(size, mix, normalization_factor)
+        if raw:
+            panels = hip_lib.preview_panels(filt, kernel, None, size[1], filter_gain=filter_gain, kernel_gain=kernel_gain)
+            split = hip_lib.preview_filter_width(size[1])
+            return panels[..., :split], panels[..., split:]
+        return _to_image(hip_lib.preview_compose(filt, kernel, None, size[1], filter_gain=filter_gain, kernel_gain=kernel_gain))
+
+    def _preview_planes(self, size, mix, normalization_factor):
+        """(filter [1, 1, H, W/2+1], its irfft2 [1, 1, H, W], not rolled) on the device: the filter built and normalised on the host as
+        for sampling, the kernel plane from the spectral kernels with a spectrum of ones."""
+        h, w = size
+        if not hip_lib.power_supported(h, w):
+            raise _device_irfft2_fallback_error(h, w)
+        device = _preview_device()
+        with utils.host_setup_threads():
+            filt = self.__class__.normalize(self.build(size), (1, 4, h, w), mix=mix, normalization_factor=normalization_factor)
+        filt = filt.to(device, torch.float32).reshape(1, 1, h, w // 2 + 1).contiguous()
+        ones = torch.ones((1, 1, h, w // 2 + 1), dtype=torch.complex64, device=device)
+        return filt, hip_lib.power_irfft2(ones, filt, (1, 1, h, w))
+
 
 def _device_irfft2_fallback_error(h, w):
     return hip_lib.SonarHipError(
@@ -252,6 +332,28 @@ class PowerNoiseItem(CustomNoiseItemBase):
             draw.draws_on_device = True
         return self.make_noise_sampler_internal(x, draw, filter_rfft, normalized=normalized)
 
+    def preview(self, size=(128, 128), noise=None, kernel_gain=1 / 3, filter_gain=1 / 3):
+        """py/nodes/powernoise.py:410-454: filter spectrum, spatial kernel and a sample of the filtered noise as one ``L`` image.  Without
+        ``noise`` the sample is the reference's: the seed-0 complex spectrum of a private host generator (no global RNG state moves),
+        uploaded once and pushed through the filter.  A ``noise`` tensor (``[1, 1, H, W]``) is filtered as it is and NOT modified -- the
+        reference multiplies its spectrum in place, which is no part of the contract.  The filter panels show the filter at mix 1."""
+        size = tuple(int(v) for v in size)
+        h, w = size
+        if not hip_lib.power_supported(h, w):
+            raise _device_irfft2_fallback_error(h, w)
+        device = _preview_device()
+        filt = self.make_filter(size, oversample=1).to(device, torch.float32).reshape(h, w // 2 + 1).contiguous()
+        if noise is None:
+            spectrum = torch.randn((1, 1, h, w // 2 + 1), dtype=torch.complex64, generator=torch.Generator().manual_seed(0))
+            sample = hip_lib.power_irfft2(spectrum.to(device), filt, (1, 1, h, w))
+        else:
+            if tuple(noise.shape[-2:]) != size or noise.numel() != h * w:
+                raise ValueError(f"preview: noise {tuple(noise.shape)} is not one {h} x {w} plane")
+            # a private copy: the caller's tensor keeps its values and its statistics tag
+            sample = hip_lib.spectral_filter(noise.detach().to(device, torch.float32, copy=True).reshape(1, 1, h, w).contiguous(), filt)
+        pfilt, kernel = self.power_filter._preview_planes(size, 1.0, getattr(self, "filter_norm_factor", 1.0))
+        return _to_image(hip_lib.preview_compose(pfilt, kernel, sample, w, filter_gain=filter_gain, kernel_gain=kernel_gain))
+
 
 class PowerFilterNoiseItem(PowerNoiseItem):
     """py/nodes/powernoise.py:462-504: a power filter applied to ANOTHER noise chain (node passes time_brownian=True)."""
@@ -270,3 +372,32 @@ class PowerFilterNoiseItem(PowerNoiseItem):
         filter_rfft = self.make_filter(x.shape)
         noise_sampler = self.noise.make_noise_sampler(x, sigma_min, sigma_max, seed, cpu, normalized=normalize_noise)
         return self.make_noise_sampler_internal(x, noise_sampler, filter_rfft, normalized=normalize_result)
+
+    def preview(self, size=(128, 128)):
+        """py/nodes/powernoise.py:524-554.  ``preview_type == "custom"``: the inner chain sampled once (seed-0 ``[1, 4, H, W]`` latent,
+        sigmas 14 -> 10), filtered, decoded by ComfyUI's latent previewer and pasted over the third panel in colour.  That needs ComfyUI's
+        ``latent_preview``; the reference's seed 0 is given to the host generator and to the current device's default generator (the one DeviceRNG
+        hands stream ids out of) inside a fork of both: they are left as they were found, and no other generator is touched."""
+        if getattr(self, "preview_type", None) != "custom":
+            return super().preview(size=size)
+        latent_preview = _host_module("latent_preview")
+        if latent_preview is None:
+            raise NotImplementedError('preview "custom" decodes the noise with ComfyUI\'s latent_preview module, which cannot be imported here')
+        formats = _host_module("comfy.latent_formats")
+        size = tuple(int(v) for v in size)
+        device = _preview_device()
+        # the reference's torch.manual_seed(0), confined: the host generator and the current device's default generator (the one DeviceRNG
+        # hands stream ids out of) are seeded inside a fork of both; torch.manual_seed itself would reseed every device and stay
+        with torch.random.fork_rng(devices=[device.index]):
+            torch.default_generator.manual_seed(0)
+            torch.cuda.manual_seed(0)
+            x = torch.randn((1, 4, *size), dtype=torch.float, device="cpu").to(device)
+            ns = self.noise.make_noise_sampler(x, torch.scalar_tensor(0.0), torch.scalar_tensor(14.0), 0, True,
+                                               normalized=self.normalize_noise is True)
+            filtered_ns = self.make_noise_sampler_internal(x, ns, self.make_filter(x.shape), self.normalize_result in {True, None})
+            filtered_noise = filtered_ns(torch.scalar_tensor(14.0), torch.scalar_tensor(10.0))
+        previewer = latent_preview.get_previewer(None, None if formats is None else formats.SD15())
+        default_preview = super().preview(size=size).convert("RGB")
+        colour = previewer.decode_latent_to_preview(filtered_noise.cpu())
+        default_preview.paste(colour.resize((size[-1], size[-2])), box=(size[-1] * 2, 0))
+        return default_preview

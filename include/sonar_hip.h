@@ -262,6 +262,23 @@ int sonar_image_noise_compose_f32(const float* noise, const float* noise_lo, con
                                   float* part_min, float* part_max, void* stream);
 int sonar_image_rescale_f32(float* image, int64_t batch, int64_t channels, int64_t plane, const float* part_min, const float* part_max,
                             float eps, void* stream);
+/* Filter previews of SonarPowerNoise / SonarPowerFilterNoise (py/nodes/powernoise.py:268-294, 410-468): two or three panels side by side,
+ * one launch per image, every roll / flip / concatenation done in the addressing.  Per plane: filter [H][W/2+1] (the normalised real
+ * half-spectrum), kernel [H][W] (its irfft2, NOT rolled), noise [H][W] or NULL (then noise_h = noise_w = 0; with a plane they must be H, W).
+ * out is [planes][H][FW + W (+ W with noise)]:
+ *   columns 0 .. FW-1      tanh(filter_gain * F) * 256, F = rfft2_to_fft2(filter) (:457-468): with Wh = W/2+1 and L = Wh-2 (Wh odd) or
+ *                          Wh-1 (Wh even), F[r][c] = filter[(r - H/2) mod H][c - L] for c >= L, and for c < L the mirror image
+ *                          filter[(H-1 - r' - H/2) mod H][L - c], r' = (r-1) mod H for an even H, r for an odd one.  FW = L + Wh, which is
+ *                          not always W (W = 6: 7 columns, W = 9: 8) -- the reference's widths
+ *   the next W columns     (tanh(kernel_gain * k) + 1) * 128, k = kernel[(r - H/2) mod H][(c - W/2) mod W]
+ *   the last W columns     (tanh(noise * (1/3)) + 1) * 128
+ * each step rounded on its own.  sonar_preview_panels_f32 writes the values as fp32; with gain == 0 it writes F, the rolled kernel and the
+ * noise as they are (data movement only), and may then be given kernel = NULL and no noise: out is [planes][H][FW], rfft2_to_fft2 itself.
+ * sonar_preview_compose_u8 writes clamp(value, 0, 255) truncated to uint8.  H, W >= 2. */
+int sonar_preview_panels_f32(const float* filter, const float* kernel, const float* noise, int64_t planes, int64_t H, int64_t W, int64_t noise_h,
+                             int64_t noise_w, float filter_gain, float kernel_gain, int gain, float* out, void* stream);
+int sonar_preview_compose_u8(const float* filter, const float* kernel, const float* noise, int64_t planes, int64_t H, int64_t W, int64_t noise_h,
+                             int64_t noise_w, float filter_gain, float kernel_gain, uint8_t* out, void* stream);
 /* RippleFilteredNoise, py/noise.py:1197-1200: x[i] *= table[(i / inner) % len] (a sin / cos gain profile along one dimension, or along
  * the flattened trailing dimensions with inner = 1); follow_sign: the result takes the sign of 1 - table[..] (torch.copysign). In place. */
 int sonar_mul_table_f32(float* x, const float* table, int64_t n, int64_t inner, int64_t len, int follow_sign, void* stream);
