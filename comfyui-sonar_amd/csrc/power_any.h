@@ -54,12 +54,29 @@ static int launch_power_any(int what, const float* z, const float* filter, float
                             uint64_t stream_id, int64_t plane_offset, int group, double* partials, NormArgs na, hipStream_t st,
                             Ahead ah = Ahead()) {
     if (what != 2) {
-        const int rc = launch_power_bucket(what, z, filter, out, planes, H, W, seed, stream_id, plane_offset, group, partials, na, st, ah);
-        if (rc != kNotABucket) return rc;
-        if (any_needs_all(H, W))
-            return launch_power_any_all(what, z, filter, out, planes, H, W, seed, stream_id, plane_offset, group, partials, na, st, ah);
+        int pairs[4];
+        const int family = any_route(H, W, pairs);
+        if (family == 2) return launch_power_bucket(what, z, filter, out, planes, H, W, seed, stream_id, plane_offset, group, partials, na, st, ah);
+        if (family == 1) return launch_power_any_all(what, z, filter, out, planes, H, W, seed, stream_id, plane_offset, group, partials, na, st, ah);
     }
     return launch_power_any_t<0, 0, 0, 0>(what, z, filter, out, planes, H, W, seed, stream_id, plane_offset, group, partials, na, st, ah);
+}
+
+// sonar_power_any_plan: what launch_power_any and launch_power_any_t decide for a plane size, through the helpers they call.
+// family < 0: as routed; 0 / 1: best_split over that family's codelet set whatever the route.
+static int any_plan_query(int64_t H, int64_t W, int family, int32_t* out) {
+    int pairs[4] = {0, 0, 0, 0};
+    if (family < 0) family = any_route(H, W, pairs);
+    AnyPlan pl;
+    AnyShape sh;
+    if (!any_plan_fill(pl, sh, H, W, pairs[0], pairs[1], pairs[2], pairs[3], family == 1 ? kSetAll : kSetSmall)) return SONAR_ERR_UNSUPPORTED;
+    // how a pass of length n runs (line_dft, line_pass1, c2r_rows): a bucket's are its compile-time codelets, else the run-time switch's
+    const int set = family == 1 ? kSetAll : kSetSmall;
+    auto runs = [&](int n, bool second) { return second && n == 1 ? 2 : (family == 2 || radix_in_set(n, set)) ? 1 : 0; };
+    const int32_t fields[12] = {family, pl.hn1, pl.hn2, pl.mn1, pl.mn2, pl.c2r_fuse, sh.nt, pl.c2r_fuse ? sh.batches : 0,
+                                runs(pl.hn1, false), runs(pl.hn2, true), runs(pl.mn1, false), runs(pl.mn2, true)};
+    for (int i = 0; i < 12; ++i) out[i] = fields[i];
+    return SONAR_OK;
 }
 
 // ---- planes beyond LDS: the same line transforms, a pass per launch through a complex workspace ---------------------------------

@@ -876,6 +876,48 @@ static inline bool any_needs_all(int64_t H, int64_t W) {
     auto big = [](int n) { return n > 1 && radix_in_set(n, kSetAll) && !radix_in_set(n, kSetSmall); };
     return big(a) || big(b) || big(c2) || big(d);
 }
+// The plan of one plane size, for the launch and for the host's query of it (sonar_power_any_plan) alike: the factor pairs -- a bucket's
+// own (bh1 > 0: they are what best_split picks among ALL codelet lengths), else best_split's over `set` --, whether the inverse rows fold
+// the pre-twiddle into their first pass, and the workgroup's shape.  false: the pairs handed in are not this size's (no such bucket).
+struct AnyShape {
+    size_t lds;   // plane buffer + twiddle tables
+    // resident workgroups: 16 waves per CU at the codelets' 128-register budget -- two 512-thread workgroups when two plane buffers fit
+    // (two planes in flight per CU: one's barriers under the other's passes), else one of 1024 threads
+    int per_cu, nt;
+    int batches;  // row batches of the folded first pass (c2r_pass0), were it taken
+};
+static inline bool any_plan_fill(AnyPlan& pl, AnyShape& sh, int64_t H, int64_t W, int bh1, int bh2, int bm1, int bm2, int set) {
+    pl.H = (int)H;
+    pl.W = (int)W;
+    pl.M = (int)W / 2;
+    pl.S = pl.M + 1;
+    if (bh1 > 0) {
+        if (bh1 * bh2 != pl.H || bm1 * bm2 != pl.M) return false;
+        pl.hn1 = bh1, pl.hn2 = bh2, pl.mn1 = bm1, pl.mn2 = bm2;
+    } else {
+        best_split(pl.H, pl.hn1, pl.hn2, set);
+        best_split(pl.M, pl.mn1, pl.mn2, set);
+    }
+    sh.lds = ((size_t)H * pl.S + H + W) * sizeof(c32);
+    sh.per_cu = 2 * (sh.lds + 1024) <= 160 * 1024 ? 2 : 1;
+    sh.nt = sh.per_cu == 2 ? kAnySlots : kAnyThreads;
+    // measured (scratch/size_sweep.py, fused against the pre-twiddle pass of its own): 104 x 152 (416 families, one batch) 155 ->
+    // 143 us, 144 x 112 (2 x 511) 142 -> 139; 96 x 96 (2 x 288) 137 -> 140, 192 x 192 and 160 x 160 (three batches) +6 %
+    const int families = pl.H * pl.mn2, most = std::max(1, sh.nt / pl.mn2);
+    sh.batches = (pl.H + most - 1) / most;
+    pl.c2r_fuse = (bh1 > 0 || codelet_len(pl.mn1, set)) && pl.mn1 > 1 && sh.batches <= 2 && 5 * families >= 4 * sh.batches * sh.nt ? 1 : 0;
+    return true;
+}
+
+// Which kernel family serves a general-size plane: 2 = an SDXL bucket's kernel with compile-time factor pairs (power_buckets.h; `pairs`
+// receives them), 1 = the kSetAll instantiation, 0 = the spill-free run-time-size kernel
+bool power_bucket_pairs(int64_t H, int64_t W, int* pairs);  // power_buckets_a.hip
+static inline int any_route(int64_t H, int64_t W, int* pairs) {
+    if (power_bucket_pairs(H, W, pairs)) return 2;
+    pairs[0] = pairs[1] = pairs[2] = pairs[3] = 0;
+    return any_needs_all(H, W) ? 1 : 0;
+}
+
 // the kernels of one call (what: as launch_power), with the plane kernel's factor pairs as template arguments (0: run time)
 constexpr int kNotABucket = -1000;
 __global__ void __launch_bounds__(kFftThreads) power_stats_any_kernel(const float* __restrict__ filter, int64_t planes, AnyPlan pl, uint64_t seed,
@@ -886,31 +928,13 @@ template <int HN1, int HN2, int MN1, int MN2, int SET = kSetSmall>
 static int launch_power_any_t(int what, const float* z, const float* filter, float* out, int64_t planes, int64_t H, int64_t W, uint64_t seed,
                               uint64_t stream_id, int64_t plane_offset, int group, double* partials, NormArgs na, hipStream_t st, Ahead ah) {
     AnyPlan pl;
-    pl.H = (int)H;
-    pl.W = (int)W;
-    pl.M = (int)W / 2;
-    pl.S = pl.M + 1;
-    if (HN1 > 0) {  // a bucket: its factor pairs are the kernel's (they are what best_split picks among ALL codelet lengths)
-        if (HN1 * HN2 != pl.H || MN1 * MN2 != pl.M) return kNotABucket;
-        pl.hn1 = HN1, pl.hn2 = HN2, pl.mn1 = MN1, pl.mn2 = MN2;
-    } else {
-        best_split(pl.H, pl.hn1, pl.hn2, SET);
-        best_split(pl.M, pl.mn1, pl.mn2, SET);
-    }
-    const size_t lds = ((size_t)H * pl.S + H + W) * sizeof(c32);
-    {
-        // measured (scratch/size_sweep.py, fused against the pre-twiddle pass of its own): 104 x 152 (416 families, one batch) 155 ->
-        // 143 us, 144 x 112 (2 x 511) 142 -> 139; 96 x 96 (2 x 288) 137 -> 140, 192 x 192 and 160 x 160 (three batches) +6 %
-        const int nt = 2 * (lds + 1024) <= 160 * 1024 ? kAnySlots : kAnyThreads;
-        const int families = pl.H * pl.mn2, batches = (pl.H + std::max(1, nt / pl.mn2) - 1) / std::max(1, nt / pl.mn2);
-        pl.c2r_fuse = (HN1 > 0 || codelet_len(pl.mn1, SET)) && pl.mn1 > 1 && batches <= 2 && 5 * families >= 4 * batches * nt ? 1 : 0;
-    }
+    AnyShape sh;
+    if (!any_plan_fill(pl, sh, H, W, HN1, HN2, MN1, MN2, SET)) return kNotABucket;
+    const size_t lds = sh.lds;
     const size_t lds_stats = (size_t)4 * H * sizeof(c32);
     const int split = group > 1 && planes / group < 512 ? 1 : 0;
     const int64_t units = split ? planes : planes / group;
-    // resident workgroups: 16 waves per CU at the codelets' 128-register budget -- two 512-thread workgroups when two plane buffers fit
-    // (two planes in flight per CU: one's barriers under the other's passes), else one of 1024 threads
-    const int per_cu = 2 * (lds + 1024) <= 160 * 1024 ? 2 : 1;
+    const int per_cu = sh.per_cu;
     // The plane kernel's units (generate mode): whole groups for the launch's full rounds of workgroups, single planes for what is left
     // when that is cheaper than a last round of whole groups on a few workgroups (a single-plane unit costs ~1.3 planes: it seeds and
     // skips).  530 latents of 104 x 152 on 512 workgroups: 2 x 4 plane-times -> 4 + 1.3 (`scratch/any_trace.py`: 14.5 us per plane).

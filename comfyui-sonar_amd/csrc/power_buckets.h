@@ -3,7 +3,8 @@
 // kernel holds exactly its four codelets instead of a run-time switch over seventeen at four call sites (which spilled 32-74 vector
 // registers in every instantiation, py/nodes/powernoise.py:356-377 is the path).  Two translation units (power_buckets_a.hip, _b.hip:
 // the codelets of 13, 14, 17 and 19 points unroll to thousands of instructions per kernel) share this header; the factor pairs are
-// checked against best_split at run time (launch_power_any_t), a bucket out of step falls back to the run-time-size kernel.
+// held to what best_split picks by tests/test_power_any_sites_cpu.py; a bucket whose pairs do not multiply to its size is no bucket
+// (power_bucket_pairs): the size takes the run-time-size kernels.
 #pragma once
 #include "power_any_core.h"
 

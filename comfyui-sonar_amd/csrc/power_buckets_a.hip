@@ -11,6 +11,19 @@ int launch_power_bucket(SONAR_BUCKET_ARGS) {
     return launch_power_bucket_b(SONAR_BUCKET_PASS);
 }
 
+// a bucket out of step with its size (the products) is no bucket: the size takes the run-time-size kernels
+bool power_bucket_pairs(int64_t H, int64_t W, int* pairs) {
+#define SONAR_BUCKET_CASE(HH, WW, A, B, C, D)                     \
+    if (H == HH && W == WW && A * B == HH && 2 * C * D == WW) {   \
+        pairs[0] = A, pairs[1] = B, pairs[2] = C, pairs[3] = D;   \
+        return true;                                              \
+    }
+    SONAR_BUCKETS_A(SONAR_BUCKET_CASE)
+    SONAR_BUCKETS_B(SONAR_BUCKET_CASE)
+#undef SONAR_BUCKET_CASE
+    return false;
+}
+
 }  // namespace sonar
 
 #ifdef SONAR_ANY_TRACE

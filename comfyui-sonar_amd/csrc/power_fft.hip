@@ -1805,6 +1805,7 @@ static bool block_plane_ok(int64_t, int64_t) { return false; }
 static bool any_ahead_ok(int64_t, int64_t, int64_t, int) { return false; }
 static int launch_power_any(int, const float*, const float*, float*, int64_t, int64_t, int64_t, uint64_t, uint64_t, int64_t, int, double*, NormArgs, hipStream_t, Ahead) { return SONAR_ERR_UNSUPPORTED; }
 static int launch_power_block(int, const float*, float*, float*, int64_t, int64_t, int64_t, uint64_t, uint64_t, int64_t, int, double*, NormArgs, hipStream_t) { return SONAR_ERR_UNSUPPORTED; }
+static int any_plan_query(int64_t, int64_t, int, int32_t*) { return SONAR_ERR_UNSUPPORTED; }
 }  // namespace sonar
 bool sonar_lines_rows_r2c(const float*, float*, int64_t, int64_t, hipStream_t) { return false; }
 bool sonar_lines_cols(const float*, const float*, float*, int64_t, int64_t, int64_t, int, hipStream_t) { return false; }
@@ -1869,6 +1870,13 @@ extern "C" int sonar_power_plane_kind(int64_t H, int64_t W) {
         if (H == f[0] && W == f[1]) return 1;
     if (any_plane_ok(H, W)) return 2;
     return block_plane_ok(H, W) ? 4 : 0;  // 4: generated in column blocks through a workspace (sonar_power_block_f32); 3 is the host's name for the direct passes
+}
+
+extern "C" int sonar_power_any_plan(int64_t H, int64_t W, int family, int32_t* out) {
+    SONAR_REQUIRE(out && family >= -1 && family <= 1, SONAR_ERR_ARG, "sonar_power_any_plan: bad argument (family -1, 0 or 1)");
+    SONAR_REQUIRE(sonar_power_plane_kind(H, W) == 2, SONAR_ERR_UNSUPPORTED,
+                  "sonar_power_any_plan: %lld x %lld is not a general-size plane (sonar_power_plane_kind != 2)", (long long)H, (long long)W);
+    return any_plan_query(H, W, family, out);
 }
 
 extern "C" int64_t sonar_power_block_ws_bytes(int64_t planes, int64_t H, int64_t W) {

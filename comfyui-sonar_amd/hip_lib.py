@@ -163,6 +163,7 @@ SIGNATURES = {
     "sonar_laplace_add_f32": (_I, [_P, _P, _F, _F, _F, _I64, _P]),
     "sonar_distro_fill_f32": (_I, [_P, _I64, _U64, _U64, _I64, C.POINTER(DistroParams), _P]),
     "sonar_power_plane_kind": (_I, [_I64, _I64]),
+    "sonar_power_any_plan": (_I, [_I64, _I64, _I, C.POINTER(C.c_int32)]),
     "sonar_power_block_ws_bytes": (_I64, [_I64, _I64, _I64]),
     "sonar_power_block_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _U64, _U64, _I64, _I, _I, _F, _F, _P, _P]),
     "sonar_rfft2_f32": (_I, [_P, _P, _I64, _I64, _I64, _P]),
@@ -2012,7 +2013,7 @@ PYRAMID_AHEAD = os.environ.get("SONAR_PYRAMID_AHEAD", "1") != "0"  # plans run a
 PERLIN_AHEAD = os.environ.get("SONAR_PERLIN_AHEAD", "1") != "0"  # plans fuse a normalised Perlin call's three launches (_PerlinAheadHook)
 NOT_RUN = object()      # Plan.run: the step was not issued (a guard changed, an entry point refused): take the ordinary path
 _M64 = 2**64 - 1
-_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_dwt_out_len",
+_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_power_any_plan", "sonar_dwt_out_len",
                            "sonar_dwt2_ws_bytes", "sonar_wcfg_lowpass_lds_bytes", "sonar_wcfg_fused_ws_bytes", "sonar_pyramid_levels",
                            "sonar_plan_fn_id", "sonar_plan_fn_nargs"))
 PATCH_SLOT, PATCH_STREAM, PATCH_SEED, PATCH_BLOB, PATCH_LEVELS = range(5)

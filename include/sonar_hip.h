@@ -672,6 +672,15 @@ int sonar_level_normal_f32(float* level, int64_t planes, int64_t h, int64_t w, f
  * sonar_dft_* passes as for kind 0, 0 = unsupported by the LDS kernels (the sonar_power_* / sonar_spectral_filter_f32 calls return -2 for
  * kinds 0 and 4). */
 int sonar_power_plane_kind(int64_t H, int64_t W);
+/* Host only, no GPU work: the plan of the general-size kernels (kind 2) for an H x W plane, as the launch itself forms it.
+ *   family  -1: as the launch routes the size; 0 / 1: the factor pairs of that family's codelet set whatever the route (what best_split
+ *           gives an SDXL bucket's size over all codelet lengths, say)
+ *   out[12] family (0 = run-time sizes with the codelets 2 .. 12, 1 = with every codelet length, 2 = an SDXL bucket's compile-time pairs),
+ *           hn1, hn2 (H = hn1 x hn2), mn1, mn2 (W / 2 = mn1 x mn2), whether the inverse rows fold the c2r pre-twiddle into their first pass,
+ *           threads per workgroup (512 or 1024), row batches of that folded pass (0 when it is not folded), then how the passes of
+ *           length hn1, hn2, mn1, mn2 run: 1 = a register codelet of that length, 0 = direct sums, 2 = absent (a second pass of length 1)
+ * SONAR_ERR_UNSUPPORTED where sonar_power_plane_kind(H, W) != 2. */
+int sonar_power_any_plan(int64_t H, int64_t W, int family, int32_t* out);
 /* Kind-4 planes, spectrum drawn on device (py/nodes/powernoise.py:338-366 -- the reference filters the rfft2 of white noise, which IS
  * a complex-normal half-spectrum: drawn directly, no forward transform):
  *   mode 0: out = irfft2(drawn * filter, norm="ortho"); statistics of out into `partials` when given
