@@ -563,7 +563,8 @@ template <typename T, typename TIO>
 static int wcfg_bands(const TIO* ta, const TIO* tb, const TIO* x, TIO* out, int64_t planes, int64_t H, int64_t W, int levels,
                       const double* dec_lo, const double* dec_hi, const double* rec_lo, const double* rec_hi, int flen, int mode_fwd, int mode_inv,
                       const double* yh_scales, double yl_scale, double ku, double kt, int subtract_from_x, hipStream_t st, const char* what) {
-    SONAR_REQUIRE(ta && out && (x || !subtract_from_x) && dec_lo && dec_hi && rec_lo && rec_hi && yh_scales && planes >= 0 && mode_fwd >= 0 &&
+    // (an empty batch has no storage: its tensors arrive as null pointers, and nothing is launched for it)
+    SONAR_REQUIRE(((ta && out && (x || !subtract_from_x)) || planes == 0) && dec_lo && dec_hi && rec_lo && rec_hi && yh_scales && planes >= 0 && mode_fwd >= 0 &&
                       mode_fwd <= 5 && mode_inv >= 0 && mode_inv <= 5,
                   SONAR_ERR_ARG, "%s: bad argument", what);
     SONAR_REQUIRE(levels >= 1 && levels <= kLowMaxLevels, SONAR_ERR_UNSUPPORTED, "%s: 1 .. %d levels", what, kLowMaxLevels);

@@ -397,7 +397,8 @@ template <typename T>
 static int wcfg_lowpass(const float* cond, const float* uncond, const float* x, float* out, int64_t planes, int64_t H, int64_t W, int levels,
                         const double* dec_lo, const double* rec_lo, int flen, int mode_fwd, int mode_inv, const double* g, double ku, double kt,
                         int subtract_from_x, hipStream_t st, const char* what) {
-    SONAR_REQUIRE(cond && uncond && out && (x || !subtract_from_x) && dec_lo && rec_lo && g && planes >= 0 && mode_fwd >= 0 && mode_fwd <= 5 &&
+    // (an empty batch has no storage: its tensors arrive as null pointers, and nothing is launched for it)
+    SONAR_REQUIRE(((cond && uncond && out && (x || !subtract_from_x)) || planes == 0) && dec_lo && rec_lo && g && planes >= 0 && mode_fwd >= 0 && mode_fwd <= 5 &&
                       mode_inv >= 0 && mode_inv <= 5,
                   SONAR_ERR_ARG, "%s: bad argument", what);
     LowArgs<T> a{};

@@ -673,7 +673,8 @@ static int wcfg_fused(const float* cond, const float* uncond, const float* x, fl
                       const double* rec_hi, int rec_len, int mode_inv, const double* yl_scales, const double* yh_scales,
                       int blend_mode, double strength, int subtract_from_x, void* ws, int64_t ws_bytes, hipStream_t st,
                       const char* what, bool perfect_reconstruction = false) {
-    SONAR_REQUIRE(cond && uncond && out && (x || !subtract_from_x) && ws && yl_scales && yh_scales && planes >= 0 && mode_fwd >= 0 &&
+    // (an empty batch has no storage: its tensors arrive as null pointers, and nothing is launched for it)
+    SONAR_REQUIRE(((cond && uncond && out && (x || !subtract_from_x)) || planes == 0) && ws && yl_scales && yh_scales && planes >= 0 && mode_fwd >= 0 &&
                       mode_fwd <= 5 && mode_inv >= 0 && mode_inv <= 5 && blend_mode >= 0 && blend_mode <= 2,
                   SONAR_ERR_ARG, "%s: bad argument", what);
     SONAR_REQUIRE(dims_ok(H, W), SONAR_ERR_UNSUPPORTED, "%s: bad plane size", what);
