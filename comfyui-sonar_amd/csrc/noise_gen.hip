@@ -1786,11 +1786,13 @@ __global__ void __launch_bounds__(kPyrBlock) pyramid_plane_kernel(float* out, in
     }
 }
 
-// true if the plane kernel was launched; *slots (optional): the number of partial pairs its workgroups own (the rest are zeroed)
-static bool launch_pyramid_plane(float* out, int64_t planes, int64_t H, int64_t W, const PyramidLevels& lv, int mode, uint64_t seed,
-                                 uint64_t stream_id, int64_t elem_offset, double* partials, hipStream_t st, Accum fold = kNoAccum,
-                                 int pre_kind = 0, Prefix pre = Prefix{1.0f, 1.0f, 1.0f, 0, 0, nullptr, 1, 0}, LatticeJob lat = kNoLattice,
-                                 int* slots = nullptr) {
+// Which kernel a level table gets, for the launch and for the host's query of it (sonar_pyramid_route) alike: 0 the flat kernel
+// (pyramid_generate_kernel), 1 the plane kernel, 2 the plane kernel with stretched rows -- and the LDS sizes the decision rests on.
+struct PyramidRoute {
+    int route;
+    size_t grid_floats, lds, lds_x;
+};
+static PyramidRoute pyramid_route(const PyramidLevels& lv, int64_t H, int64_t W, int mode, int64_t elem_offset) {
     size_t grid_floats = 0, rows = 0;
     for (int l = 0; l < lv.count; ++l) {
         grid_floats += (size_t)lv.h[l] * lv.w[l];
@@ -1799,8 +1801,21 @@ static bool launch_pyramid_plane(float* out, int64_t planes, int64_t H, int64_t 
     grid_floats = (grid_floats + 3) & ~(size_t)3;  // the coordinate tables that follow are 16-byte entries
     const size_t lds = grid_floats * sizeof(float) + (mode == 0 || mode == 2 ? (size_t)lv.count * (H + W) * sizeof(Lin) : 0);
     const size_t lds_x = lds + rows * W * sizeof(float);
-    if (W % 4 != 0 || elem_offset % (H * W) != 0 || lds > kPyramidLdsBudget) return false;
-    const bool xrows = mode == 0 && W % 4 == 0 && lds_x <= kPyramidLdsBudget;
+    int route = 1;
+    if (W % 4 != 0 || elem_offset % (H * W) != 0 || lds > kPyramidLdsBudget) route = 0;
+    else if (mode == 0 && lds_x <= kPyramidLdsBudget) route = 2;
+    return PyramidRoute{route, grid_floats, lds, lds_x};
+}
+
+// true if the plane kernel was launched; *slots (optional): the number of partial pairs its workgroups own (the rest are zeroed)
+static bool launch_pyramid_plane(float* out, int64_t planes, int64_t H, int64_t W, const PyramidLevels& lv, int mode, uint64_t seed,
+                                 uint64_t stream_id, int64_t elem_offset, double* partials, hipStream_t st, Accum fold = kNoAccum,
+                                 int pre_kind = 0, Prefix pre = Prefix{1.0f, 1.0f, 1.0f, 0, 0, nullptr, 1, 0}, LatticeJob lat = kNoLattice,
+                                 int* slots = nullptr) {
+    const PyramidRoute r = pyramid_route(lv, H, W, mode, elem_offset);
+    if (r.route == 0) return false;
+    const size_t grid_floats = r.grid_floats, lds = r.lds, lds_x = r.lds_x;
+    const bool xrows = r.route == 2;
     const int g = (int)std::min<int64_t>(planes, kNPart);
     if (slots) *slots = g;
     const bool nt = nt_stores_host(planes * H * W);
@@ -2566,6 +2581,26 @@ static int pyramid_common(const char* what, float* out, int64_t planes, int64_t 
     SONAR_REQUIRE(W % 4 == 0 && aligned16(out) && elem_offset % 4 == 0, SONAR_ERR_UNSUPPORTED,
                   "%s: needs W %% 4 == 0 and 16-byte aligned output", what);
     return SONAR_OK;
+}
+
+extern "C" int sonar_pyramid_route(int64_t H, int64_t W, int64_t nlevels, const int64_t* level_h, const int64_t* level_w, int mode,
+                                   int64_t elem_offset) {
+    SONAR_REQUIRE(H > 0 && W > 0 && nlevels >= 0 && (nlevels == 0 || (level_h && level_w)) && mode >= 0 && mode <= 2 && elem_offset >= 0,
+                  SONAR_ERR_ARG, "sonar_pyramid_route: bad argument");
+    PyramidLevels lv{};
+    bool folded = false;
+    for (int64_t l = 0; l < nlevels; ++l) {
+        SONAR_REQUIRE(level_h[l] > 0 && level_w[l] > 0, SONAR_ERR_ARG, "sonar_pyramid_route: bad argument");
+        if (!folded && level_h[l] == H && level_w[l] == W) {  // as fill_levels takes a NULL level of the latent's own size: no grid
+            folded = true;
+            continue;
+        }
+        SONAR_REQUIRE(lv.count < kMaxLevels, SONAR_ERR_UNSUPPORTED, "sonar_pyramid_route: too many levels");
+        lv.h[lv.count] = (int)level_h[l];
+        lv.w[lv.count] = (int)level_w[l];
+        ++lv.count;
+    }
+    return pyramid_route(lv, H, W, mode, elem_offset).route;
 }
 
 extern "C" int sonar_pyramid_generate_f32(float* out, int64_t planes, int64_t H, int64_t W, int64_t nlevels,

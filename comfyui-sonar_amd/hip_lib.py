@@ -129,6 +129,7 @@ SIGNATURES = {
     "sonar_perlin_noise_ahead_f32": (_I, [_P, _P, _I64, _I64, _F, _U64, _U64, _I64, _F, _F, _P, _I, _U64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _U64, _P]),
     "sonar_resample_acc_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _F, _I, _I, _P, _P]),
     "sonar_pyramid_generate_f32": (_I, [_P, _I64, _I64, _I64, _I64, C.POINTER(_P), _PI64, _PI64, _PF, _I, _U64, _U64, _I64, _P, _P]),
+    "sonar_pyramid_route": (_I, [_I64, _I64, _I64, _PI64, _PI64, _I, _I64]),
     "sonar_pyramid_noise_f32": (_I, [_P, _I64, _I64, _I64, _I64, C.POINTER(_P), _PI64, _PI64, _PF, _I, _U64, _U64, _I64, _F, _F, _P, _P]),
     "sonar_pyramid_noise_ahead_f32": (_I, [_P, _I64, _I64, _I64, _I64, _PI64, _PI64, _PF, _I, _U64, _U64, _I64, _F, _F, _P, _I, _U64, _I64, _PI64, _PI64, _PF, _P,
                                            _P]),
@@ -1130,6 +1131,19 @@ def pyramid_generate(shape, device, levels: Sequence, mode: str, seed: int, stre
     return out
 
 
+def pyramid_route(H: int, W: int, levels: Sequence, mode: str, elem_offset: int = 0) -> int:
+    """The kernel a pyramid call with this level list gets (``sonar_pyramid_route``, host only): 0 the flat kernel, 1 the plane kernel, 2 the
+    plane kernel with stretched rows.  ``levels`` as ``pyramid_generate`` takes them, or (h, w) pairs."""
+    sizes = [(lv[-3], lv[-2]) if len(lv) > 2 else (lv[0], lv[1]) for lv in levels]
+    n = len(sizes)
+    hs = (C.c_int64 * max(n, 1))(*[int(s[0]) for s in sizes])
+    ws = (C.c_int64 * max(n, 1))(*[int(s[1]) for s in sizes])
+    rc = load().sonar_pyramid_route(int(H), int(W), n, hs, ws, RESAMPLE_IDS[mode], int(elem_offset))
+    if rc < 0:
+        _check(rc, "sonar_pyramid_route")
+    return rc
+
+
 def pyramid_generate_acc_(y: torch.Tensor, y_mul: float, x_mul: float, levels: Sequence, mode: str, seed: int, stream_id: int,
                           elem_offset: int = 0, partials=None, pre: Optional[FoldPrefix] = None) -> bool:
     """y[B, C, H, W] <- y * y_mul + pyramid * x_mul (the values of ``pyramid_generate``) in place; ``pre``: the previous chain item's fold,
@@ -2014,7 +2028,7 @@ PERLIN_AHEAD = os.environ.get("SONAR_PERLIN_AHEAD", "1") != "0"  # plans fuse a 
 NOT_RUN = object()      # Plan.run: the step was not issued (a guard changed, an entry point refused): take the ordinary path
 _M64 = 2**64 - 1
 _HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_power_any_plan", "sonar_dwt_out_len",
-                           "sonar_dwt2_ws_bytes", "sonar_wcfg_lowpass_lds_bytes", "sonar_wcfg_fused_ws_bytes", "sonar_pyramid_levels",
+                           "sonar_dwt2_ws_bytes", "sonar_wcfg_lowpass_lds_bytes", "sonar_wcfg_fused_ws_bytes", "sonar_pyramid_levels", "sonar_pyramid_route",
                            "sonar_plan_fn_id", "sonar_plan_fn_nargs"))
 PATCH_SLOT, PATCH_STREAM, PATCH_SEED, PATCH_BLOB, PATCH_LEVELS = range(5)
 

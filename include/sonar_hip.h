@@ -627,6 +627,13 @@ int sonar_pyramid_generate_f32(float* out, int64_t planes, int64_t H, int64_t W,
                                const float* const* level_ptrs /*host array of device ptrs*/, const int64_t* level_h,
                                const int64_t* level_w, const float* level_weight, int mode, uint64_t seed,
                                uint64_t stream_id, int64_t elem_offset, double* partials /*nullable*/, void* stream);
+/* Host only, no GPU work: which kernel the pyramid entry points give a level list, by the arithmetic the launch itself uses (the LDS the
+ * grids, the coordinate tables and the stretched rows take against the 64 KB budget, W % 4, whole planes): 0 = the flat kernel (supplied
+ * grids only: a level drawn in the kernel is refused there), 1 = the plane kernel, 2 = the plane kernel with stretched rows.  level_h /
+ * level_w are the caller's list; its first level of the latent's own size counts as drawn (folded into the base draw: it takes no LDS).
+ * The kernel route only: the 16-byte alignment and the argument checks stay with the entry points.  SONAR_ERR_UNSUPPORTED for more than
+ * 12 grids. */
+int sonar_pyramid_route(int64_t H, int64_t W, int64_t nlevels, const int64_t* level_h, const int64_t* level_w, int mode, int64_t elem_offset);
 
 /* same, with the normaliser folded in (see sonar_perlin_noise_f32) */
 int sonar_pyramid_noise_f32(float* out, int64_t planes, int64_t H, int64_t W, int64_t nlevels,

@@ -8,6 +8,15 @@ tests compare the kernels against it, so a wrong lane, tile, stream word or conv
 ``STREAM_VERSION`` is the ``sonar_noise_stream_version()`` this statement describes.  A change to generate-mode values bumps the
 library's version and updates this file in the same change (tests/test_gpu_generate_oracle.py checks that the two agree).
 
+The pyramid family (tests/test_gpu_pyramid_oracle.py holds the kernels to it) rests on three rules:
+  pyramid_level_grid  the grid the plane kernel draws for a level passed with a NULL pointer: the burst rng_stream(seed, stream_id + 2 +
+                      level index in the CALLER's list, tile = global plane elem_offset / (H W) + p, lane = slot); slot t of
+                      min(256, ceil(h w / 4)) owns the elements 4t .. 4t + 3, then 4(t + 256) .., one normal4 per group.
+  level_normal        the level value of sonar_levels_sampled_f32 / sonar_level_normal_f32 at the global element index
+                      e = (plane_offset + p) h w + y w + x: slot e % 4 of philox_normal4(seed, stream, e // 4); level l uses stream_id + l.
+  pyramid_planes      normal_fill * sqrt(1 + w0^2) (fp32; 1 without a NULL level of the latent's own size) + sum_l w_l resize(grid_l), the
+                      grids drawn as above or supplied.  The resampler is the caller's (tests/pyramid_refs.py: ATen's index rules, fp64 sums).
+
 Kernel sources cited below are under comfyui-sonar_amd/csrc/.
 """
 from __future__ import annotations
@@ -193,6 +202,69 @@ def philox_normal4(seed: int, stream: int, group):
     """common.h philox_normal4: the four normals of one Philox block, counter (group, stream), key seed -> [..., 4] fp64."""
     w = philox_group(seed, stream, group)
     return _normal4(np.stack(w, axis=-1))
+
+
+# ------------------------------------------------------------------------------------------------ pyramid streams (noise_gen.hip: pyramid_plane_body, fill_levels, level_normal)
+PYRAMID_SLOTS = 256        # noise_gen.hip kBlock: generator slots of one drawn level grid
+PYRAMID_MAX_LEVELS = 12    # noise_gen.hip kMaxLevels
+
+
+def pyramid_level_grid(seed: int, stream_id: int, level_index: int, plane: int, h: int, w: int):
+    """The [h, w] grid the plane kernel draws for the level at ``level_index`` of the CALLER's list (a level passed with a NULL pointer; a
+    full-resolution level folded into the base draw still takes its index) and the global plane ``plane`` = elem_offset / (H W) + p.
+    Slot t of min(256, ceil(h w / 4)) runs the burst rng_stream(seed, stream_id + 2 + level_index, tile = plane, lane = t) and owns the
+    elements 4t .. 4t + 3, then 4(t + 256) .., one normal4 (four words, two Box-Muller pairs) per group; a cut last group drops its tail."""
+    n = int(h) * int(w)
+    slots = min(PYRAMID_SLOTS, -(-n // 4))
+    rounds = -(-n // (4 * PYRAMID_SLOTS))
+    stream = (int(stream_id) + 2 + int(level_index)) & (2**64 - 1)
+    rng = rng_stream(seed, stream, np.full(slots, int(plane), dtype=np.uint64), np.arange(slots, dtype=np.uint64))
+    z = _normal4(rng.words(4 * rounds).reshape(slots, rounds, 4))     # [slot, round, 4]: element 4 slot + 1024 round + k
+    return z.transpose(1, 0, 2).reshape(-1)[:n].reshape(int(h), int(w))
+
+
+def level_normal(seed: int, stream: int, e):
+    """noise_gen.hip level_normal: the level value at the global element index e = (plane_offset + p) h w + y w + x is slot e % 4 of
+    philox_normal4(seed, stream, e // 4).  Level l of a sonar_levels_sampled_f32 call uses the stream id stream_id + l."""
+    e = np.asarray(e, dtype=np.int64)
+    z = philox_normal4(seed, int(stream) & (2**64 - 1), (e // 4).astype(np.uint64))
+    return np.take_along_axis(z, (e % 4)[..., None], axis=-1)[..., 0]
+
+
+def pyramid_base_scale(levels, H: int, W: int) -> float:
+    """fill_levels: sqrt(1 + w0^2) in fp32 when a level (grid None) of the latent's own size is present -- it is folded into the base draw,
+    the sum of two independent normals drawn as one -- else 1."""
+    for grid, h, w, wt in levels:
+        if grid is None and (h, w) == (H, W):
+            w0 = np.float32(wt)
+            return float(np.sqrt(np.float32(1.0) + w0 * w0, dtype=np.float32))
+    return 1.0
+
+
+def pyramid_planes(seed: int, stream_id: int, planes: int, H: int, W: int, levels, mode: str, elem_offset: int, resize, magnitude: bool = False):
+    """sonar_pyramid_generate_f32 in fp64, [planes, H, W]: normal_fill(seed, stream_id, planes H W, elem_offset) * base_scale
+    + sum_l w_l resize(grid_l), with ``levels`` = [(grid or None, h, w, weight), ...] as the caller lists them: a supplied grid is a
+    [planes, h, w] array, None at the latent's own size is the folded level (pyramid_base_scale), None at any other size is drawn
+    (pyramid_level_grid with the level's index in this list and the global plane elem_offset / (H W) + p: whole planes only).
+    ``resize(grids [planes, h, w], H, W, mode)`` -> [planes, H, W] is the caller's fp64 resampler; weights are rounded to fp32 as the C ABI
+    takes them.  ``magnitude``: also the per-value scale base_scale |z| + sum_l |w_l| max |grid_l| that fp32 rounding errors are relative to."""
+    n = planes * H * W
+    base = pyramid_base_scale(levels, H, W)
+    out = normal_fill(seed, stream_id, n, elem_offset).reshape(planes, H, W) * base
+    mag = np.abs(out)
+    folded = False
+    for l, (grid, h, w, wt) in enumerate(levels):
+        if grid is None and (h, w) == (H, W) and not folded:
+            folded = True
+            continue
+        if grid is None:
+            assert elem_offset % (H * W) == 0, "drawn level grids are keyed by whole global planes"
+            grid = np.stack([pyramid_level_grid(seed, stream_id, l, elem_offset // (H * W) + p, h, w) for p in range(planes)])
+        grid = np.asarray(grid, dtype=np.float64).reshape(planes, h, w)
+        wt = float(np.float32(wt))
+        out = out + wt * resize(grid, H, W, mode)
+        mag = mag + abs(wt) * np.abs(grid).max()
+    return (out, mag) if magnitude else out
 
 
 # ------------------------------------------------------------------------------------------------ Brownian z(node, e) (noise_gen.hip:1980-2180, 2296-2321)

@@ -139,6 +139,79 @@ def test_brownian_families_and_selector():
     assert np.array_equal(zl[0, 8:], ds.philox_normal4(22, 9, np.arange(2)).reshape(-1))
 
 
+# ------------------------------------------------------------------------------------------------ pyramid streams
+def _scalar_normal4(words):
+    ra, rb, rc, rd = (int(v) for v in words)
+    a, b = ds.box_muller(ra, rb)
+    c, d = ds.box_muller(rc, rd)
+    return [float(a), float(b), float(c), float(d)]
+
+
+@pytest.mark.parametrize("h, w", [(1, 1), (3, 3), (5, 7), (21, 20), (33, 33)])
+def test_pyramid_level_grid_by_a_scalar_walk(h, w):
+    """Element i of a drawn level grid, one at a time: slot (i // 4) % 256 of the level's bursts, stepped to round i // 1024, value i % 4 of
+    that round's four words -- the burst of (stream_id + 2 + level index, plane, slot)."""
+    seed, stream, level, plane = 2**64 - 1, 2**47 + 1, 3, 2**33 + 7
+    grid = ds.pyramid_level_grid(seed, stream, level, plane, h, w).reshape(-1)
+    n = h * w
+    assert grid.shape == (n,)
+    for i in sorted({0, min(n - 1, 1), min(n - 1, 2), n - 1, n // 2, min(n - 1, 1023), min(n - 1, 1024), min(n - 1, 1027)}):
+        slot, rnd = (i // 4) % 256, i // 1024
+        g = ds.rng_stream(seed, stream + 2 + level, plane, slot)
+        words = g.words(4 * (rnd + 1))[4 * rnd:]
+        assert grid[i] == _scalar_normal4(words)[i % 4], i
+
+
+def test_pyramid_level_grid_slots_and_keys():
+    seed, stream = 2**32 + 5, 2**32 + 3
+    # 1089 elements: 256 slots, slot 0 draws a second group (elements 1024 .. 1027) that continues its burst
+    g = ds.pyramid_level_grid(seed, stream, 0, 4, 33, 33).reshape(-1)
+    burst = ds.rng_stream(seed, stream + 2, 4, 0).words(8)
+    assert list(g[:4]) == _scalar_normal4(burst[:4]) and list(g[1024:1028]) == _scalar_normal4(burst[4:])
+    assert list(g[4:8]) == _scalar_normal4(ds.rng_stream(seed, stream + 2, 4, 1).words(4))
+    # 35 elements: nine slots, the last group cut after three values
+    g35 = ds.pyramid_level_grid(seed, stream, 0, 4, 5, 7).reshape(-1)
+    assert list(g35[32:]) == _scalar_normal4(ds.rng_stream(seed, stream + 2, 4, 8).words(4))[:3]
+    # the level's index in the caller's list and the global plane both key the burst: every value changes
+    base = ds.pyramid_level_grid(seed, stream, 1, 4, 21, 20)
+    assert np.all(ds.pyramid_level_grid(seed, stream, 2, 4, 21, 20) != base)
+    assert np.all(ds.pyramid_level_grid(seed, stream, 1, 5, 21, 20) != base)
+    assert np.array_equal(ds.pyramid_level_grid(seed, stream + 1, 0, 4, 21, 20), base)   # stream_id + 2 + index is all that enters
+    assert abs(base.std() - 1.0) < 0.1
+
+
+def test_level_normal_is_a_slot_of_philox_normal4():
+    seed, stream = 2**64 - 1, 2**32 + 3
+    e = np.array([0, 1, 2, 3, 4, 35, 38, 2**34 + 1, 2**34 + 6])
+    z = ds.level_normal(seed, stream, e)
+    for i, ei in enumerate(e):
+        assert z[i] == ds.philox_normal4(seed, stream, int(ei) // 4)[int(ei) % 4]
+    assert ds.level_normal(seed, stream, 7).shape == () and ds.level_normal(seed, stream, e.reshape(3, 3)).shape == (3, 3)
+    assert np.all(ds.level_normal(seed, stream + 1, e) != z)
+
+
+def test_pyramid_planes_of_a_shard_is_the_slice_of_the_whole():
+    from tests import pyramid_refs as R
+
+    seed, stream, H, W = 2**32 + 5, 2**47 + 1, 8, 12
+    rng = np.random.default_rng(5)
+    sup = rng.standard_normal((6, 3, 3))
+    levels = [(None, 9, 9, 0.7), (None, H, W, 1.0), (sup, 3, 3, 0.49), (None, 5, 7, -0.3)]
+    whole, mag = ds.pyramid_planes(seed, stream, 6, H, W, levels, "bilinear", 0, R.resize, magnitude=True)
+    assert whole.shape == mag.shape == (6, H, W) and np.all(mag >= np.abs(whole) - 1e-12)
+    for k, n in ((1, 2), (4, 2), (0, 6)):
+        shard_levels = [(g if g is None else g[k:k + n], h, w, wt) for g, h, w, wt in levels]
+        assert np.array_equal(ds.pyramid_planes(seed, stream, n, H, W, shard_levels, "bilinear", k * H * W, R.resize), whole[k:k + n])
+    # the parts: base draw times sqrt(1 + w0^2) in fp32, drawn levels by their index in the caller's list (0 and 3), the supplied one as given
+    z = ds.normal_fill(seed, stream, 6 * H * W).reshape(6, H, W) * float(np.sqrt(np.float32(2.0)))
+    assert ds.pyramid_base_scale(levels, H, W) == float(np.sqrt(np.float32(2.0))) and ds.pyramid_base_scale(levels[:1], H, W) == 1.0
+    g0 = np.stack([ds.pyramid_level_grid(seed, stream, 0, p, 9, 9) for p in range(6)])
+    g3 = np.stack([ds.pyramid_level_grid(seed, stream, 3, p, 5, 7) for p in range(6)])
+    want = z + float(np.float32(0.7)) * R.resize(g0, H, W, "bilinear") + float(np.float32(0.49)) * R.resize(sup, H, W, "bilinear") \
+        + float(np.float32(-0.3)) * R.resize(g3, H, W, "bilinear")
+    assert np.allclose(whole, want, rtol=0, atol=1e-13)
+
+
 # ------------------------------------------------------------------------------------------------ half-spectrum draw orders
 @pytest.mark.parametrize("shape", list(ds.FIXED_PLANES) + [(104, 152), (96, 168), (256, 256)])
 def test_every_half_spectrum_element_is_drawn_once(shape):
