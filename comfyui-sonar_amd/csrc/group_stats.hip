@@ -19,6 +19,12 @@
 // Accumulation: rowstats_kernel's (elementwise.hip) -- sum and sum of squares in fp64 (a product of two floats is exact in a double), mean
 // = s / n, var = (q - s * mean) / (n - 1), the same last lines (finish_mean_std) -- with the partial sums of lanes, waves and slices added
 // in fp64 in a fixed order.  n == 1 gives 0 / 0 = NaN like torch.  Min / max are fminf / fmaxf folds as in minmax_rows_kernel.
+//
+// The same two sweeps carry two more per-group results (the `X` parameter of the kernels):
+//   peak          amax of x or of |x| with torch.amax's NaN (amax_mid_kernel's fold): PowerLawNoiseGenerator's div_max_dims over any dims,
+//                 followed by x / peak[g] in place (group_div_kernel);
+//   divided mean  the mean of x / d[g], every quotient rounded to fp32 first and added in fp64: scale_rows_kernel's second statistic, so
+//                 that scale_noise(normalize_dims=...) over any dims is group_stats (std) -> divided mean -> group_scale_noise_kernel.
 #include "common.h"
 
 namespace sonar {
@@ -71,21 +77,37 @@ __device__ __forceinline__ uint32_t group_of(const Segs& sg, uint32_t i) {
     return g;
 }
 
-template <bool MS, bool MM>
+constexpr int kPlain = 0, kPeak = 1, kPeakAbs = 2, kDivMean = 3;  // X: what else a sweep accumulates (MS and MM false; kDivMean: MS alone)
+
+template <bool MS, bool MM, int X = kPlain>
 struct Acc {
     double s = 0.0, q = 0.0;
     float lo = INFINITY, hi = -INFINITY;
+    float d = 1.0f;    // kDivMean: the group's divisor
+    bool nan = false;  // kPeak / kPeakAbs: a member was NaN
     __device__ __forceinline__ void add(float f) {
-        if constexpr (MS) {
-            const double v = f;
-            s += v;
-            q += v * v;
-        }
-        if constexpr (MM) {
-            lo = fminf(lo, f);
-            hi = fmaxf(hi, f);
+        if constexpr (X == kDivMean) {
+            s += (double)(f / d);
+        } else if constexpr (X != kPlain) {
+            fold(X == kPeakAbs ? fabsf(f) : f);
+        } else {
+            if constexpr (MS) {
+                const double v = f;
+                s += v;
+                q += v * v;
+            }
+            if constexpr (MM) {
+                lo = fminf(lo, f);
+                hi = fmaxf(hi, f);
+            }
         }
     }
+    // kPeak / kPeakAbs: another lane's, wave's or slice's peak() joins
+    __device__ __forceinline__ void fold(float v) {
+        nan |= v != v;
+        hi = fmaxf(hi, v);
+    }
+    __device__ __forceinline__ float peak() const { return nan ? NAN : hi; }  // torch.amax propagates NaN
 };
 
 // rowstats_kernel's last lines
@@ -97,9 +119,19 @@ __device__ __forceinline__ void finish_mean_std(double s, double q, uint32_t n, 
 }
 
 // what a (group, slice) leaves: the final values (S == 1) or its partials, plane p of the workspace at ws[(p * S + slice) * G + g]
-template <bool MS, bool MM>
-__device__ __forceinline__ void leave(const Acc<MS, MM>& a, uint32_t g, uint32_t sl, uint32_t G, uint32_t R, uint32_t S, float* mean,
+// (kPeak / kPeakAbs: the peak goes to hi, one plane; kDivMean: the mean to `mean`, one plane)
+template <bool MS, bool MM, int X>
+__device__ __forceinline__ void leave(const Acc<MS, MM, X>& a, uint32_t g, uint32_t sl, uint32_t G, uint32_t R, uint32_t S, float* mean,
                                       float* stdv, float* lo, float* hi, double* ws) {
+    if constexpr (X == kDivMean) {
+        if (S == 1) mean[g] = (float)(a.s / (double)R);
+        else ws[(size_t)sl * G + g] = a.s;
+        return;
+    } else if constexpr (X != kPlain) {
+        if (S == 1) hi[g] = a.peak();
+        else ws[(size_t)sl * G + g] = (double)a.peak();
+        return;
+    }
     if (S == 1) {
         if constexpr (MS) finish_mean_std(a.s, a.q, R, mean + g, stdv + g);
         if constexpr (MM) {
@@ -120,7 +152,7 @@ __device__ __forceinline__ void leave(const Acc<MS, MM>& a, uint32_t g, uint32_t
 }
 
 // innermost segment reduced: a wave per (group, slice), lanes over consecutive members
-template <bool MS, bool MM>
+template <bool MS, bool MM, int X = kPlain>
 __global__ void __launch_bounds__(kBlock) group_stats_runs_kernel(const float* __restrict__ x, Segs sg, uint32_t G, uint32_t R, uint32_t S,
                                                                    uint32_t chunk, float* mean, float* stdv, float* lo, float* hi, double* ws) {
     kernarg_touch_for(x, sg, G, R, S, chunk, mean, stdv, lo, hi, ws);
@@ -130,7 +162,8 @@ __global__ void __launch_bounds__(kBlock) group_stats_runs_kernel(const float* _
         const uint32_t g = (uint32_t)(item / S), sl = (uint32_t)(item - (uint64_t)g * S);
         const float* base = x + offset_of<false>(sg, g);
         const uint32_t e0 = sl * chunk, e1 = min(R, e0 + chunk);  // e0 < R: no slice is empty (split_of)
-        Acc<MS, MM> a;
+        Acc<MS, MM, X> a;
+        if constexpr (X == kDivMean) a.d = stdv[g];  // (the divisor table comes in stdv's place)
         uint32_t e = e0 + lane;
         for (; e + 3 * 64 < e1; e += 4 * 64) {  // four independent loads per lane in flight
             const float v0 = base[offset_of<true>(sg, e)], v1 = base[offset_of<true>(sg, e + 64)];
@@ -140,7 +173,7 @@ __global__ void __launch_bounds__(kBlock) group_stats_runs_kernel(const float* _
         for (; e < e1; e += 64) a.add(base[offset_of<true>(sg, e)]);
         if constexpr (MS) {
             a.s = wave_sum(a.s);
-            a.q = wave_sum(a.q);
+            if constexpr (X == kPlain) a.q = wave_sum(a.q);
         }
         if constexpr (MM) {
 #pragma unroll
@@ -149,12 +182,16 @@ __global__ void __launch_bounds__(kBlock) group_stats_runs_kernel(const float* _
                 a.hi = fmaxf(a.hi, __shfl_down(a.hi, off, 64));
             }
         }
-        if (lane == 0) leave<MS, MM>(a, g, sl, G, R, S, mean, stdv, lo, hi, ws);
+        if constexpr (X == kPeak || X == kPeakAbs) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) a.fold(__shfl_down(a.peak(), off, 64));
+        }
+        if (lane == 0) leave<MS, MM, X>(a, g, sl, G, R, S, mean, stdv, lo, hi, ws);
     }
 }
 
 // innermost segment kept: a lane per (group, slice), workgroups over 256 consecutive groups
-template <bool MS, bool MM>
+template <bool MS, bool MM, int X = kPlain>
 __global__ void __launch_bounds__(kBlock) group_stats_lanes_kernel(const float* __restrict__ x, Segs sg, uint32_t G, uint32_t R, uint32_t S,
                                                                     uint32_t chunk, float* mean, float* stdv, float* lo, float* hi, double* ws) {
     kernarg_touch_for(x, sg, G, R, S, chunk, mean, stdv, lo, hi, ws);
@@ -166,7 +203,8 @@ __global__ void __launch_bounds__(kBlock) group_stats_lanes_kernel(const float* 
         if (g >= G) continue;
         const float* base = x + offset_of<false>(sg, g);
         const uint32_t e0 = sl * chunk, e1 = min(R, e0 + chunk);
-        Acc<MS, MM> a;
+        Acc<MS, MM, X> a;
+        if constexpr (X == kDivMean) a.d = stdv[g];
         uint32_t e = e0;  // the same for every lane: the offsets below are the wave's, not the lane's
         for (; e + 3 < e1; e += 4) {
             const float v0 = base[offset_of<true>(sg, e)], v1 = base[offset_of<true>(sg, e + 1)];
@@ -174,18 +212,28 @@ __global__ void __launch_bounds__(kBlock) group_stats_lanes_kernel(const float* 
             a.add(v0); a.add(v1); a.add(v2); a.add(v3);
         }
         for (; e < e1; ++e) a.add(base[offset_of<true>(sg, e)]);
-        leave<MS, MM>(a, g, sl, G, R, S, mean, stdv, lo, hi, ws);
+        leave<MS, MM, X>(a, g, sl, G, R, S, mean, stdv, lo, hi, ws);
     }
 }
 
 // the slices of a group, added in slice order
-template <bool MS, bool MM>
+template <bool MS, bool MM, int X = kPlain>
 __global__ void __launch_bounds__(kBlock) group_stats_combine_kernel(const double* __restrict__ ws, uint32_t G, uint32_t R, uint32_t S,
                                                                       float* mean, float* stdv, float* lo, float* hi) {
     kernarg_touch_for(ws, G, R, S, mean, stdv, lo, hi);
     const size_t plane = (size_t)S * G;
     for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < G; g += (uint64_t)gridDim.x * kBlock) {
-        Acc<MS, MM> a;
+        Acc<MS, MM, X> a;
+        if constexpr (X != kPlain) {  // one plane
+            for (uint32_t sl = 0; sl < S; ++sl) {
+                const double v = ws[(size_t)sl * G + g];
+                if constexpr (X == kDivMean) a.s += v;
+                else a.fold((float)v);
+            }
+            if constexpr (X == kDivMean) mean[g] = (float)(a.s / (double)R);
+            else hi[g] = a.peak();
+            continue;
+        }
         for (uint32_t sl = 0; sl < S; ++sl) {
             const size_t at = (size_t)sl * G + g;
             if constexpr (MS) {
@@ -223,6 +271,23 @@ __global__ void __launch_bounds__(kBlock) group_minmax_rescale_kernel(const floa
     for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
         const uint32_t g = group_of(sg, (uint32_t)i);
         out[i] = minmax_rescale_value(x[i], lo[g], hi[g], eps, tmin, tmax, span);
+    }
+}
+
+// PowerLawNoiseGenerator's `noise /= amax(...)` (py/noise_generation.py:780-785) with the peak of the element's group: a true division
+__global__ void __launch_bounds__(kBlock) group_div_kernel(float* x, Segs sg, uint32_t total, const float* __restrict__ d) {
+    kernarg_touch_for(x, sg, total, d);
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock)
+        x[i] = x[i] / d[group_of(sg, (uint32_t)i)];
+}
+
+// scale_rows_kernel's last pass (elementwise.hip; py/utils.py:97-99) with the (std, mean of x / std) of the element's group
+__global__ void __launch_bounds__(kBlock) group_scale_noise_kernel(float* x, Segs sg, uint32_t total, const float* __restrict__ sd,
+                                                                    const float* __restrict__ mean, float factor) {
+    kernarg_touch_for(x, sg, total, sd, mean, factor);
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t g = group_of(sg, (uint32_t)i);
+        x[i] = (x[i] / sd[g] - mean[g]) * factor;
     }
 }
 
@@ -298,20 +363,20 @@ void split_of(const Layout& lay, uint32_t* S, uint32_t* chunk) {
     *S = (uint32_t)((R + c - 1) / c);
 }
 
-template <bool MS, bool MM>
+template <bool MS, bool MM, int X = kPlain>
 void launch_stats(const Layout& lay, const float* x, float* mean, float* stdv, float* lo, float* hi, double* ws, hipStream_t st) {
     uint32_t S, chunk;
     split_of(lay, &S, &chunk);
     const uint32_t G = (uint32_t)lay.groups, R = (uint32_t)lay.members;
     if (lay.inner_reduced) {
-        hipLaunchKernelGGL((group_stats_runs_kernel<MS, MM>), dim3(grid_for((int64_t)G * S, kBlock / 64)), dim3(kBlock), 0, st, x, lay.sg, G, R, S,
+        hipLaunchKernelGGL((group_stats_runs_kernel<MS, MM, X>), dim3(grid_for((int64_t)G * S, kBlock / 64)), dim3(kBlock), 0, st, x, lay.sg, G, R, S,
                            chunk, mean, stdv, lo, hi, ws);
     } else {
-        hipLaunchKernelGGL((group_stats_lanes_kernel<MS, MM>), dim3(grid_for((int64_t)((G + kBlock - 1) / kBlock) * S, 1)), dim3(kBlock), 0, st, x,
+        hipLaunchKernelGGL((group_stats_lanes_kernel<MS, MM, X>), dim3(grid_for((int64_t)((G + kBlock - 1) / kBlock) * S, 1)), dim3(kBlock), 0, st, x,
                            lay.sg, G, R, S, chunk, mean, stdv, lo, hi, ws);
     }
     if (S > 1)
-        hipLaunchKernelGGL((group_stats_combine_kernel<MS, MM>), dim3(grid_for(G, kBlock)), dim3(kBlock), 0, st, ws, G, R, S, mean, stdv, lo, hi);
+        hipLaunchKernelGGL((group_stats_combine_kernel<MS, MM, X>), dim3(grid_for(G, kBlock)), dim3(kBlock), 0, st, ws, G, R, S, mean, stdv, lo, hi);
 }
 
 int64_t ws_doubles(const Layout& lay, bool ms, bool mm) {
@@ -391,4 +456,62 @@ extern "C" int sonar_group_adjust_f32(int op, const float* v, int64_t n, float k
     SONAR_REQUIRE(v && out, SONAR_ERR_ARG, "sonar_group_adjust_f32: bad argument");
     hipLaunchKernelGGL(group_adjust_kernel, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, op, v, n, k, out);
     return check_launch("sonar_group_adjust_f32");
+}
+
+// ---- PowerLawNoiseGenerator's div_max_dims and scale_noise's normalize_dims over any dims ----------------------------------------------
+// ws of the two reductions: what sonar_group_stats_ws_doubles names for one pair (they keep one plane of its two)
+extern "C" int sonar_group_peak_f32(const float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                                    int64_t s5, int use_abs, float* peak, double* ws, void* stream) {
+    const int64_t sizes[kMaxSegs] = {s0, s1, s2, s3, s4, s5};
+    Layout lay;
+    const int rc = layout_of("sonar_group_peak_f32", nseg, first_reduced, sizes, &lay);
+    if (rc != 0) return rc;
+    if (lay.total == 0) return SONAR_OK;
+    SONAR_REQUIRE(x && peak && (const void*)peak != x && (const void*)ws != x, SONAR_ERR_ARG, "sonar_group_peak_f32: bad argument");
+    SONAR_REQUIRE(ws || ws_doubles(lay, false, true) == 0, SONAR_ERR_ARG, "sonar_group_peak_f32: this shape is split and needs the workspace");
+    const hipStream_t st = (hipStream_t)stream;
+    if (use_abs) launch_stats<false, false, kPeakAbs>(lay, x, nullptr, nullptr, nullptr, peak, ws, st);
+    else launch_stats<false, false, kPeak>(lay, x, nullptr, nullptr, nullptr, peak, ws, st);
+    return check_launch("sonar_group_peak_f32");
+}
+
+extern "C" int sonar_group_div_f32(float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                                   int64_t s5, const float* d, void* stream) {
+    const int64_t sizes[kMaxSegs] = {s0, s1, s2, s3, s4, s5};
+    Layout lay;
+    const int rc = layout_of("sonar_group_div_f32", nseg, first_reduced, sizes, &lay);
+    if (rc != 0) return rc;
+    if (lay.total == 0) return SONAR_OK;
+    SONAR_REQUIRE(x && d && (const void*)d != x, SONAR_ERR_ARG, "sonar_group_div_f32: bad argument");
+    hipLaunchKernelGGL(group_div_kernel, dim3(grid_for(lay.total, kBlock * 2)), dim3(kBlock), 0, (hipStream_t)stream, x, lay.sg,
+                       (uint32_t)lay.total, d);
+    return check_launch("sonar_group_div_f32");
+}
+
+extern "C" int sonar_group_divided_mean_f32(const float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3,
+                                            int64_t s4, int64_t s5, const float* d, float* mean, double* ws, void* stream) {
+    const int64_t sizes[kMaxSegs] = {s0, s1, s2, s3, s4, s5};
+    Layout lay;
+    const int rc = layout_of("sonar_group_divided_mean_f32", nseg, first_reduced, sizes, &lay);
+    if (rc != 0) return rc;
+    if (lay.total == 0) return SONAR_OK;
+    SONAR_REQUIRE(x && d && mean && mean != d && (const void*)mean != x && (const void*)ws != x, SONAR_ERR_ARG,
+                  "sonar_group_divided_mean_f32: bad argument");
+    SONAR_REQUIRE(ws || ws_doubles(lay, true, false) == 0, SONAR_ERR_ARG,
+                  "sonar_group_divided_mean_f32: this shape is split and needs the workspace");
+    launch_stats<true, false, kDivMean>(lay, x, mean, const_cast<float*>(d), nullptr, nullptr, ws, (hipStream_t)stream);
+    return check_launch("sonar_group_divided_mean_f32");
+}
+
+extern "C" int sonar_group_scale_noise_f32(float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                                           int64_t s5, const float* sd, const float* mean, float factor, void* stream) {
+    const int64_t sizes[kMaxSegs] = {s0, s1, s2, s3, s4, s5};
+    Layout lay;
+    const int rc = layout_of("sonar_group_scale_noise_f32", nseg, first_reduced, sizes, &lay);
+    if (rc != 0) return rc;
+    if (lay.total == 0) return SONAR_OK;
+    SONAR_REQUIRE(x && sd && mean && (const void*)sd != x && (const void*)mean != x, SONAR_ERR_ARG, "sonar_group_scale_noise_f32: bad argument");
+    hipLaunchKernelGGL(group_scale_noise_kernel, dim3(grid_for(lay.total, kBlock * 2)), dim3(kBlock), 0, (hipStream_t)stream, x, lay.sg,
+                       (uint32_t)lay.total, sd, mean, factor);
+    return check_launch("sonar_group_scale_noise_f32");
 }

@@ -134,6 +134,10 @@ const Replayable kReplayable[] = {
     SONAR_REPLAYABLE(sonar_group_affine_f32),
     SONAR_REPLAYABLE(sonar_group_minmax_rescale_f32),
     SONAR_REPLAYABLE(sonar_group_adjust_f32),
+    SONAR_REPLAYABLE(sonar_group_peak_f32),
+    SONAR_REPLAYABLE(sonar_group_div_f32),
+    SONAR_REPLAYABLE(sonar_group_divided_mean_f32),
+    SONAR_REPLAYABLE(sonar_group_scale_noise_f32),
 };
 #undef SONAR_REPLAYABLE
 constexpr int kReplayableCount = (int)(sizeof(kReplayable) / sizeof(kReplayable[0]));

@@ -195,6 +195,10 @@ SIGNATURES = {
     "sonar_group_affine_f32": (_I, [_I, _P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "sonar_group_minmax_rescale_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _F, _D, _D, _P, _P]),
     "sonar_group_adjust_f32": (_I, [_I, _P, _I64, _F, _P, _P]),
+    "sonar_group_peak_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _P, _P]),
+    "sonar_group_div_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P]),
+    "sonar_group_divided_mean_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "sonar_group_scale_noise_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _F, _P]),
     "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
@@ -1814,6 +1818,59 @@ def group_adjust(op: int, v: torch.Tensor, k: float) -> torch.Tensor:
     out = torch.empty_like(v)
     _check(load().sonar_group_adjust_f32(op, _dev(v, "v"), v.numel(), float(k), _dev(out, "out"), _stream()), "sonar_group_adjust_f32")
     return out
+
+
+def _group_ws(lib, seg, mean_std: bool, device):
+    """The workspace a split reduction over ``seg`` needs (None: not split)."""
+    need = lib.sonar_group_stats_ws_doubles(*seg, int(mean_std), int(not mean_std))
+    if need < 0:
+        _check(need, "sonar_group_stats_ws_doubles")
+    return torch.empty(need, dtype=torch.float64, device=device) if need else None
+
+
+def group_peak(x: torch.Tensor, dims, use_abs: bool) -> torch.Tensor:
+    """``torch.amax(|x| if use_abs else x, dim=dims, keepdim=True)`` as a flat tensor, on ``x`` as it lies."""
+    seg, groups = _segment_args(x.shape, dims)
+    lib = load()
+    peak = torch.empty(groups, dtype=torch.float32, device=x.device)
+    ws = _group_ws(lib, seg, False, x.device)
+    _check(lib.sonar_group_peak_f32(_dev(x, "x"), *seg, int(bool(use_abs)), _dev(peak, "peak"), _opt(ws, "ws", torch.float64), _stream()),
+           "sonar_group_peak_f32")
+    return peak
+
+
+def group_div_(x: torch.Tensor, dims, d: torch.Tensor) -> torch.Tensor:
+    """``x /= d`` with the ``d`` of the element's group over ``dims``, in place (a true division)."""
+    seg, _groups = _segment_args(x.shape, dims)
+    _check(load().sonar_group_div_f32(_dev(x, "x"), *seg, _dev(d, "d"), _stream()), "sonar_group_div_f32")
+    return x
+
+
+GROUP_FEW = 1024  # groups below which a reduction with the innermost segment kept is nearly all slices (group_scale_noise_slow)
+
+
+def group_scale_noise_slow(shape, dims) -> bool:
+    """True where ``group_scale_noise_`` was measured slower than the row kernel between two transposed copies: the innermost segment kept
+    and few groups, so that the two sweeps are cut into hundreds of slices per group (512 x 4 x 128 x 128 over (0, 2): 512 groups of
+    65536, 395 us against 377 us)."""
+    sizes, first, groups = group_segments(shape, dims)
+    inner_reduced = ((len(sizes) - 1) & 1) != first
+    return not inner_reduced and groups < GROUP_FEW
+
+
+def group_scale_noise_(x: torch.Tensor, dims, factor: float) -> torch.Tensor:
+    """``scale_noise_rows_`` over any ``dims``, in place on ``x`` as it lies: per group the unbiased std (``sonar_group_stats_f32``), the
+    mean of ``x / std`` (``sonar_group_divided_mean_f32``), then ``(x / std - mean) * factor``: the row kernel's three passes."""
+    seg, groups = _segment_args(x.shape, dims)
+    lib = load()
+    mean_x, std, mean = (torch.empty(groups, dtype=torch.float32, device=x.device) for _ in range(3))
+    ws = _group_ws(lib, seg, True, x.device)
+    px, pw = _dev(x, "x"), _opt(ws, "ws", torch.float64)
+    _check(lib.sonar_group_stats_f32(px, *seg, _dev(mean_x, "mean_x"), _dev(std, "std"), None, None, pw, _stream()), "sonar_group_stats_f32")
+    _check(lib.sonar_group_divided_mean_f32(px, *seg, _dev(std, "std"), _dev(mean, "mean"), pw, _stream()), "sonar_group_divided_mean_f32")
+    _check(lib.sonar_group_scale_noise_f32(px, *seg, _dev(std, "std"), _dev(mean, "mean"), float(factor), _stream()),
+           "sonar_group_scale_noise_f32")
+    return x
 
 
 # ------------------------------------------------------------------------------------------------ SonarNoiseImage

@@ -1075,19 +1075,29 @@ class PowerLawNoiseGenerator(NoiseGenerator):
     def ng_params(cls):
         return super().ng_params() | {"alpha": 2.0, "div_max_dims": None, "use_sign": False, "use_div_max_abs": True}
 
+    @staticmethod
+    def div_max_route(dims, shape):
+        """The kernels that divide by the peak over ``dims`` of a tensor of ``shape``.  None without ``div_max_dims``; ("mid", outer, mid, inner) for a run of adjacent dimensions (``amax_mid`` / ``div_mid_``);
+        ("group", dims) for any other choice: the strided pair of csrc/group_stats.hip, which takes at most six alternating segments."""
+        if dims is None:
+            return None
+        nd = len(shape)
+        dims = tuple(range(nd)) if dims == () else sorted({d % nd for d in ((dims,) if isinstance(dims, int) else dims)})
+        if list(dims) == list(range(dims[0], dims[-1] + 1)):
+            return "mid", math.prod(shape[: dims[0]]), math.prod(shape[d] for d in dims), math.prod(shape[dims[-1] + 1:])
+        hip_lib.group_segments(shape, dims)  # more than six segments: refused here, before the draw takes an RNG position
+        return "group", tuple(dims)
+
     def generate(self, *_args):
+        route = self.div_max_route(self.div_max_dims, tuple(self.shape))
         noise = hip_lib.powerlaw_(self.rand_like().contiguous(), self.alpha, self.use_sign)
-        if self.div_max_dims is not None:
-            dims = self.div_max_dims
-            dims = tuple(range(noise.ndim)) if dims == () else sorted({d % noise.ndim for d in ((dims,) if isinstance(dims, int) else dims)})
-            if list(dims) != list(range(dims[0], dims[-1] + 1)):
-                raise hip_lib.SonarHipError("powerlaw: div_max_dims must be adjacent dimensions on the HIP path")
-            outer = math.prod(noise.shape[: dims[0]])
-            mid = math.prod(noise.shape[d] for d in dims)
-            inner = math.prod(noise.shape[dims[-1] + 1:])
-            peak = hip_lib.amax_mid(noise, outer, mid, inner, self.use_div_max_abs)
-            hip_lib.div_mid_(noise, outer, mid, inner, peak)
-        return noise
+        if route is None:
+            return noise
+        if route[0] == "mid":
+            peak = hip_lib.amax_mid(noise, *route[1:], self.use_div_max_abs)
+            return hip_lib.div_mid_(noise, *route[1:], peak)
+        peak = hip_lib.group_peak(noise, route[1], self.use_div_max_abs)
+        return hip_lib.group_div_(noise, route[1], peak)
 
 
 class WaveletFilteredNoiseGenerator(FramesToChannelsNoiseGenerator):

@@ -143,10 +143,16 @@ def scale_noise(noise: Tensor, factor: float = 1.0, *, normalized: bool = True, 
         raise hip_lib.SonarHipError("scale_noise: expects a contiguous float32 tensor")
     if normalize_dims is not None:
         pop_stats(noise)
-        rows_last, inverse = dims_last(noise, normalize_dims)
+        dims = sorted({d % noise.ndim for d in normalize_dims})
+        trailing = dims == list(range(noise.ndim - len(dims), noise.ndim))
+        if not trailing and not hip_lib.group_scale_noise_slow(noise.shape, dims):
+            # not the trailing dimensions: the row kernel's three passes on the tensor as it lies (csrc/group_stats.hip), no transposed copy
+            return hip_lib.group_scale_noise_(noise, dims, factor)
+        # trailing dimensions, or the one layout measured faster through a transposed copy (few groups, the contiguous dimension kept)
+        rows_last, inverse = dims_last(noise, dims)
         inner = 1
-        for d in range(noise.ndim - len({d % noise.ndim for d in normalize_dims}), noise.ndim):
-            inner *= rows_last.shape[d]
+        for d in dims:
+            inner *= noise.shape[d]
         return dims_restore(hip_lib.scale_noise_rows_(rows_last, n // inner, inner, factor), inverse)
     partials = pop_stats(noise)
     if partials is None:

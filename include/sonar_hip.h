@@ -328,6 +328,14 @@ int sonar_minmax_rescale_f32(const float* x, int64_t rows, int64_t inner, const 
  *  sonar_group_minmax_rescale_f32  sonar_minmax_rescale_f32's arithmetic with lo[g], hi[g]; out may be x
  *  sonar_group_adjust_f32          NormalizeToScaleNoise's per-group scalars, n values: op 0 out = v * k; op 1 t = (v - 1) * k + 1,
  *                                  out = 1e-07 where t == 0 (NaN stays NaN); out may be v
+ *  sonar_group_peak_f32            per group amax of x (use_abs 0) or |x| (use_abs 1), NaN where a member is NaN (torch.amax over any tuple of
+ *                                  dims: PowerLawNoiseGenerator's div_max_dims, py/noise_generation.py:780-785).  Split like
+ *                                  sonar_group_stats_f32; ws: sonar_group_stats_ws_doubles(..., 0, 1) doubles
+ *  sonar_group_div_f32             x /= d[g] in place, a true division (a zero d gives torch's inf / NaN)
+ *  sonar_group_divided_mean_f32    per group mean of x / d[g], every quotient rounded to fp32 and added in fp64 (the second statistic of
+ *                                  sonar_scale_noise_rows_f32: py/utils.py:97-99).  ws: sonar_group_stats_ws_doubles(..., 1, 0) doubles
+ *  sonar_group_scale_noise_f32     x = (x / sd[g] - mean[g]) * factor in place, each step rounded on its own: the last pass of
+ *                                  sonar_scale_noise_rows_f32 with the operands of the element's group
  * SONAR_ERR_ARG: nseg outside 1..6, a negative size, a required pointer NULL, a result of sonar_group_stats_f32 (or ws) equal to x, an
  * operand table equal to out, a split shape without ws.  SONAR_ERR_UNSUPPORTED: 2^31 elements or more.  A size of 0 launches nothing. */
 #define SONAR_GROUP_MAX_SEGMENTS 6
@@ -341,6 +349,14 @@ int sonar_group_minmax_rescale_f32(const float* x, int nseg, int first_reduced, 
                                    int64_t s5, const float* lo, const float* hi, float eps, double target_min, double target_max,
                                    float* out, void* stream);
 int sonar_group_adjust_f32(int op, const float* v, int64_t n, float k, float* out, void* stream);
+int sonar_group_peak_f32(const float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                         int64_t s5, int use_abs, float* peak, double* ws, void* stream);
+int sonar_group_div_f32(float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4, int64_t s5,
+                        const float* d, void* stream);
+int sonar_group_divided_mean_f32(const float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                                 int64_t s5, const float* d, float* mean, double* ws, void* stream);
+int sonar_group_scale_noise_f32(float* x, int nseg, int first_reduced, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4,
+                                int64_t s5, const float* sd, const float* mean, float factor, void* stream);
 
 /* ---------------------------------------------------------------- latent operations under CFG */
 /* SonarApplyLatentOperationCFG (py/nodes/latent_operations.py:246-300): the arithmetic on either side of the latent operations, one launch
