@@ -199,6 +199,8 @@ SIGNATURES = {
     "sonar_group_div_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     "sonar_group_divided_mean_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "sonar_group_scale_noise_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _F, _P]),
+    "sonar_shuffle_gather_f32": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _I, _P, _I, _P]),
+    "sonar_shuffle_generate_f32": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _I, _F, _I, _U64, _U64, _I64, _P]),
     "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
@@ -1874,6 +1876,38 @@ def group_scale_noise_(x: torch.Tensor, dims, factor: float) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ SonarNoiseImage
+# ------------------------------------------------------------------------------------------------ per-row shuffles (csrc/shuffle.hip)
+SHUFFLE_MAX_N = 4096  # SONAR_SHUFFLE_MAX_N: the longest dimension whose sort keys the generate kernel ranks in LDS
+
+
+def _shuffle_shape(x: torch.Tensor, dim: int):
+    if not 1 <= x.ndim <= 5:
+        raise SonarHipError(f"shuffle: a tensor of {x.ndim} dimensions; the kernels take 1 to 5")
+    return (x.ndim, *x.shape, *([1] * (5 - x.ndim)), int(dim))
+
+
+def shuffle_gather(x: torch.Tensor, dim: int, idx: torch.Tensor, *, offsets: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sonar_shuffle_gather_f32: ``x`` with every row along ``dim`` permuted by the caller's int32 ``idx`` -- a table [rows][n] of source
+    positions, or with ``offsets`` one rotation per row (negative: the row is copied).  A new tensor unless ``out`` is given."""
+    out = torch.empty_like(x) if out is None else out
+    _check(load().sonar_shuffle_gather_f32(_dev(x, "x"), _dev(out, "out"), *_shuffle_shape(x, dim), _dev(idx, "idx", torch.int32), int(bool(offsets)),
+                                           _stream()), "sonar_shuffle_gather_f32")
+    return out
+
+
+def shuffle_generate(x: torch.Tensor, dim: int, prob: float, no_identity: bool, seed: int, stream_id: int, row_offset: int = 0, *,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sonar_shuffle_generate_f32: the same gather with the mask, the rotation or the sort keys of row ``row_offset + r`` drawn in the kernel
+    from streams ``stream_id`` .. ``stream_id + 2`` of ``seed``.  Sort keys: ``dim`` of at most SHUFFLE_MAX_N."""
+    if not no_identity and 1 <= x.ndim <= 5 and -x.ndim <= dim < x.ndim and x.shape[dim] > SHUFFLE_MAX_N:
+        raise NotImplementedError(f"shuffle along a dimension of {x.shape[dim]} values: the device draw ranks at most SHUFFLE_MAX_N = "
+                                  f"{SHUFFLE_MAX_N} sort keys per row (use cpu noise)")
+    out = torch.empty_like(x) if out is None else out
+    _check(load().sonar_shuffle_generate_f32(_dev(x, "x"), _dev(out, "out"), *_shuffle_shape(x, dim), float(prob), int(bool(no_identity)),
+                                             seed & (2**64 - 1), int(stream_id), int(row_offset), _stream()), "sonar_shuffle_generate_f32")
+    return out
+
+
 IMAGE_BLEND_IDS = BLEND_IDS | {"simple_add": 3}  # SONAR_IMAGE_BLEND_ADD
 IMAGE_NPART, IMAGE_MAX_CHANNELS = 1024, 64       # SONAR_IMAGE_NPART, SONAR_IMAGE_MAX_CHANNELS
 

@@ -742,6 +742,52 @@ class QuantileFilteredNoise(CustomNoiseItemBase):
         return noise_sampler
 
 
+class ShuffledNoise(CustomNoiseItemBase):
+    """py/noise.py:1896-1948: a chain's noise, scaled, then shuffled row by row along each of ``dims`` in turn
+    (utils.elementwise_shuffle_by_dim; entry i with ``percentages[i % len(percentages)]``).  A chain built with ``cpu=True`` shuffles in
+    replay mode: the permutations come from torch's global host generator as the reference's do (under ``fork_rng`` when asked).  Otherwise
+    they are drawn in the kernel: call c, entry i takes the streams 3 (c len(dims) + i) .. + 2 of the sampler's ``seed`` (a host draw when
+    there is none, as RepeatedNoise takes its own), so two entries of one call never share a permutation."""
+
+    def clone_key(self, k):
+        if k == "noise":
+            return self.noise.clone()
+        return super().clone_key(k)
+
+    def make_noise_sampler(self, x, sigma_min, sigma_max, *args, normalized=True, **kwargs):
+        factor = self.factor
+        dims = tuple(d if d >= 0 else x.ndim + d for d in self.dims)
+        if not all(d >= 0 and d < x.ndim for d in dims):
+            raise ValueError("Dimension out of range")
+        percentages = self.percentages
+        if not all(0.0 <= p <= 1.0 for p in percentages):
+            raise ValueError("Percentage out of range, must be between 0 and 1")
+        ns = self.noise.make_noise_sampler(x, *args, sigma_min=sigma_min, sigma_max=sigma_max, normalized=normalized, **kwargs)
+        if not percentages or not dims or all(p == 0 for p in percentages):
+            return ns
+        n_percentages = len(percentages)
+        fork_rng, no_identity = self.fork_rng, self.no_identity
+        replay = kwargs.get("cpu", args[1] if len(args) > 1 else True)
+        seed = kwargs.get("seed", args[0] if args else None)
+        if seed is None and not replay:
+            seed = torch.randint(-0xFFFF_FFFF, 0xFFFF_FFFF, (1,), device="cpu", dtype=torch.int64).item()
+        calls = 0
+
+        def noise_sampler(sigma, sigma_next):
+            nonlocal calls
+            noise = scale_noise(ns(sigma, sigma_next), factor, normalized=normalized)
+            pop_stats(noise)  # the shuffles hand back new tensors: the tag would describe this one
+            first = 3 * len(dims) * calls
+            calls += 1
+            with torch.random.fork_rng(enabled=bool(fork_rng and replay), devices=()):
+                for idx, dim in enumerate(dims):
+                    noise = utils.elementwise_shuffle_by_dim(noise, dim=dim, prob=percentages[idx % n_percentages], no_identity=no_identity,
+                                                             device_key=None if replay else (seed, first + 3 * idx))
+            return noise
+
+        return noise_sampler
+
+
 class RNGStates:
     """py/utils.py:736-791: a snapshot of Python's ``random``, torch's CPU generator and the current device's default generator, which
     can be put back (``set_states``) and taken again (``update``).  The device generator is captured as (seed, Philox offset): generate

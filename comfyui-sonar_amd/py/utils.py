@@ -216,6 +216,47 @@ def normalize_to_scale_adv(t: Tensor, *, min_pos: float, max_pos: float, min_neg
     return hip_lib.signed_rescale(x, 1, x.numel(), min_neg, max_neg, min_pos, max_pos)
 
 
+def elementwise_shuffle_by_dim(t: Tensor, *, dim: int = -1, prob: float = 1.0, no_identity: bool = False, generator=None,
+                               device_key: Optional[tuple] = None) -> Tensor:
+    """py/utils.py:599-657: every row of ``t`` along ``dim`` (one position of the other dimensions) shuffled on its own with probability
+    ``prob`` -- rotated by a non-zero offset with ``no_identity``, permuted by the order of ``n`` uniform sort keys otherwise.  A gather on
+    the tensor as it lies (csrc/shuffle.hip), a new tensor.
+
+    ``device_key`` None is replay mode: the mask, then the offsets or the keys are drawn on the host with the reference's calls, shapes and
+    order (``generator``, or torch's global host generator), sorted there and uploaded as int32, so after ``torch.manual_seed(s)`` the
+    result is the reference's on the CPU copy of ``t``.  ``device_key`` = (seed, stream) is generate mode: the kernel draws them from streams
+    ``stream`` .. ``stream + 2`` by global row, nothing but the tensor is read or written.  A negative ``dim`` counts
+    from the end (the reference only takes ``dim >= 0``)."""
+    from . import noise_generation
+
+    _require_device(t, "elementwise_shuffle_by_dim")
+    nd = t.ndim
+    if not -nd <= dim < nd:
+        raise IndexError(f"Dimension out of range (expected to be in range of [{-max(nd, 1)}, {max(nd, 1) - 1}], but got {dim})")
+    if t.numel() == 0:
+        return t.clone()
+    d = dim % nd
+    x = as_f32(t)
+    n = x.shape[d]
+    rows = x.numel() // n
+    if device_key is not None:
+        seed, stream = device_key
+        shard = noise_generation.current_batch_offset()
+        if shard != 0 and d == 0:
+            raise NotImplementedError("elementwise_shuffle_by_dim: dim 0 shuffles across the samples of the batch, which a sharded batch splits")
+        out = hip_lib.shuffle_generate(x, d, prob, no_identity, seed, stream, shard * (rows // x.shape[0]))
+    else:
+        mask = torch.rand(rows, device="cpu", generator=generator) < prob if prob < 1.0 else torch.ones(rows, device="cpu", dtype=torch.bool)
+        if no_identity:
+            offsets = torch.randint(1, n, (rows,), device="cpu", generator=generator)
+            idx = torch.where(mask, offsets, -1)
+        else:
+            idx = torch.arange(n, device="cpu").expand(rows, -1).clone()
+            idx[mask] = torch.rand(rows, n, device="cpu", generator=generator)[mask].argsort(dim=1)
+        out = hip_lib.shuffle_gather(x, d, idx.to(torch.int32).to(x.device), offsets=no_identity)
+    return out if t.dtype == torch.float32 else out.to(t.dtype)
+
+
 def tensor_to(tensor: Tensor, dest) -> Tensor:
     """py/utils.py:112-121."""
     device = dest.device if isinstance(dest, Tensor) else dest

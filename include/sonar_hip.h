@@ -408,6 +408,29 @@ int sonar_noise_params_scan(int src_dtype, const void* src, int64_t planes, int6
 int sonar_noise_params_apply(int src_dtype, const void* src, int dst_dtype, void* out, int64_t planes, int64_t plane_in, int64_t plane_out,
                              int fix_invalid, int normalized, float factor, float threshold_std_devs, const double* partials, void* stream);
 
+/* ---------------------------------------------------------------- ShuffledNoise */
+/* utils.elementwise_shuffle_by_dim (py/utils.py:599-657): every row of a contiguous fp32 tensor of `ndim` <= 5 dimensions s0.. permuted
+ * along dimension `dim` on its own, on the tensor as it lies (no transposed copy).  n = the size of `dim`, rows = the other sizes'
+ * product, row r = the row-major position of the other dimensions: with inner = the product of the sizes behind `dim`, value j of row r
+ * lies at ((r / inner) * n + j) * inner + r % inner -- the strides follow from the shape.  Every output value is an input value.
+ *  sonar_shuffle_gather_f32    replay mode, the permutation from the host: out[r, j] = src[r, idx[r * n + j]] (idx_is_offset 0: an int32
+ *                              table [rows][n], entries in [0, n) -- not checked) or out[r, j] = src[r, (j + idx[r]) % n] (idx_is_offset 1:
+ *                              one int32 per row in [0, n); a negative entry copies the row).
+ *  sonar_shuffle_generate_f32  generate mode, the permutation drawn in the kernel from (seed, stream_id, row_offset + r) -- the stream
+ *                              contract is INTEGRATION.md 3b: row r is shuffled when prob >= 1 or its mask variate (stream_id) is below
+ *                              prob and copied otherwise; with no_identity a shuffled row is rotated by an offset in [1, n) (stream_id + 1),
+ *                              otherwise value j moves to the rank of its key among the row's n keys (stream_id + 2), ranked in LDS by
+ *                              (key, j).  No table reaches memory.  Keys: n <= SONAR_SHUFFLE_MAX_N.
+ * SONAR_ERR_ARG: a NULL pointer, out == src, ndim outside 1..5, dim outside [0, ndim), a negative size, n < 1 (n < 2 with offsets or
+ * no_identity), more than 2^31 rows, prob NaN, row_offset < 0, row_offset + rows or stream_id + 2 not below 2^48.  SONAR_ERR_UNSUPPORTED:
+ * keys with n > SONAR_SHUFFLE_MAX_N.  All checked before anything is launched; rows == 0 launches nothing. */
+#define SONAR_SHUFFLE_MAX_N 4096
+#define SONAR_SHUFFLE_DOMAIN 0x53484646u
+int sonar_shuffle_gather_f32(const float* src, float* out, int ndim, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4, int dim,
+                             const int32_t* idx, int idx_is_offset, void* stream);
+int sonar_shuffle_generate_f32(const float* src, float* out, int ndim, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4, int dim,
+                               float prob, int no_identity, uint64_t seed, uint64_t stream_id, int64_t row_offset, void* stream);
+
 /* A pending global normalisation of a noise tensor (py/utils.py:100-105): the decision scale_noise(normalized=True) would take,
  * computed ON THE DEVICE from the tensor's (sum, sumsq) partials and left in device memory, so that the kernel that consumes the
  * noise (the sampler-step kernels below take it as `noise_norm`, nullable) applies `((v - mean) / std) * factor` -- only the parts
