@@ -17,6 +17,18 @@ The pyramid family (tests/test_gpu_pyramid_oracle.py holds the kernels to it) re
   pyramid_planes      normal_fill * sqrt(1 + w0^2) (fp32; 1 without a NULL level of the latent's own size) + sum_l w_l resize(grid_l), the
                       grids drawn as above or supplied.  The resampler is the caller's (tests/pyramid_refs.py: ATen's index rules, fp64 sums).
 
+The Perlin family (tests/test_gpu_perlin_oracle.py holds the kernels to it) rests on three rules:
+  perlin_lattice_revolutions  the corner angles, in revolutions: lattice point p = (c (H + 1) + gy)(W + 1) + gx of iteration `it` is u01 of
+                      word it % 4 of Philox4x32-10 with counter (p lo, p hi, it // 4, stream id TRUNCATED to 32 bits), key = seed.  The
+                      lattice is shared by every latent and every shard: no element offset enters it.
+  perlin_lattice      the summed cell-centre terms [C, H, W]: gradient (cos 2 pi u, sin 2 pi u), corner offsets (+-0.5, +-0.5), the blend of
+                      common.h at t = 0.5 over the rows first, then the columns, summed over the iterations (none: zeros).
+  perlin_values       output index i of a call is u01(stream word of the global element elem_offset + i) / div_fac + sum_t terms[t][i % chw]:
+                      the uniform fill's word per element (stream_words), the term tables repeating per latent of the CALL (a shard starts
+                      on a latent boundary).  Its float32_steps restates the roundings; perlin_rounding_bound derives the fp32 error bound.
+PerlinOldNoiseGenerator takes two stream ids (device_key(2)): the base draw uses `stream`, the lattice `stream + 1`; a shard's elem_offset is
+its first latent times C H W.
+
 Kernel sources cited below are under comfyui-sonar_amd/csrc/.
 """
 from __future__ import annotations
@@ -202,6 +214,112 @@ def philox_normal4(seed: int, stream: int, group):
     """common.h philox_normal4: the four normals of one Philox block, counter (group, stream), key seed -> [..., 4] fp64."""
     w = philox_group(seed, stream, group)
     return _normal4(np.stack(w, axis=-1))
+
+
+# ------------------------------------------------------------------------------------------------ Perlin (noise_gen.hip: perlin_lattice_cells, perlin_generate_kernel, perlin_fast_tiles; common.h Divider)
+PERLIN_BLENDS = ("lerp", "inject", "subtract_b")  # common.h blend, SONAR_BLEND_* 0 / 1 / 2
+
+
+def perlin_lattice_revolutions(seed: int, stream: int, iters: int, C: int, H: int, W: int):
+    """The corner angles of perlin_lattice_cells as fractions of a revolution, [iters, C, H + 1, W + 1] fp64 (exact 24-bit values).  Lattice
+    point p = (c (H + 1) + gy)(W + 1) + gx of iteration ``it`` is u01(word it % 4) of Philox4x32-10 with counter (p lo, p hi, it // 4, stream)
+    and key ``seed``.  Only the low 32 bits of the stream id reach the counter (its fourth word): the streams s and s + 2^32 give one
+    lattice.  That is what the kernel does; the tile-keyed draws (rng_stream) use 48 bits."""
+    seed, stream = int(seed) & (2**64 - 1), int(stream) & 0xFFFFFFFF
+    pts = int(C) * (int(H) + 1) * (int(W) + 1)
+    p = np.arange(pts, dtype=np.uint64)
+    out = np.zeros((int(iters), pts), dtype=np.float64)
+    for g in range(0, int(iters), 4):
+        w = philox4x32_10(p & U32, p >> np.uint64(32), np.full_like(p, g >> 2), np.full_like(p, stream), seed & 0xFFFFFFFF, seed >> 32)
+        for k in range(min(4, int(iters) - g)):
+            out[g + k] = u01(w[k])
+    return out.reshape(int(iters), int(C), int(H) + 1, int(W) + 1)
+
+
+def perlin_blend(mode: str, a, b, t: float = 0.5):
+    """common.h blend in fp64: lerp a + t (b - a), inject b t + a, subtract_b a - b t."""
+    if mode == "lerp":
+        return a + t * (b - a)
+    if mode == "inject":
+        return b * t + a
+    if mode == "subtract_b":
+        return a - b * t
+    raise KeyError(mode)
+
+
+def perlin_cell_terms(revolutions, blend_mode: str):
+    """Cell-centre terms [..., H, W] of corner angles [..., H + 1, W + 1] in revolutions: gradient (cos, sin) of 2 pi u, dot products with the
+    offsets TL (0.5, 0.5), TR (-0.5, 0.5), BL (0.5, -0.5), BR (-0.5, -0.5), blended at t = 0.5 over the rows (TL-TR, BL-BR), then the columns."""
+    a = 2.0 * math.pi * np.asarray(revolutions, dtype=np.float64)
+    gx, gy = np.cos(a), np.sin(a)
+    tl = gx[..., :-1, :-1] * 0.5 + gy[..., :-1, :-1] * 0.5
+    tr = gx[..., :-1, 1:] * -0.5 + gy[..., :-1, 1:] * 0.5
+    bl = gx[..., 1:, :-1] * 0.5 + gy[..., 1:, :-1] * -0.5
+    br = gx[..., 1:, 1:] * -0.5 + gy[..., 1:, 1:] * -0.5
+    return perlin_blend(blend_mode, perlin_blend(blend_mode, tl, tr), perlin_blend(blend_mode, bl, br))
+
+
+def perlin_lattice(seed: int, stream: int, iters: int, C: int, H: int, W: int, blend_mode: str):
+    """sonar_perlin_lattice_f32 in fp64: the sum over the iterations of the cell-centre terms, [C, H, W]; no iterations give zeros."""
+    if int(iters) <= 0:
+        return np.zeros((int(C), int(H), int(W)), dtype=np.float64)
+    return perlin_cell_terms(perlin_lattice_revolutions(seed, stream, iters, C, H, W), blend_mode).sum(axis=0)
+
+
+def divisor_is_power_of_two(div_fac) -> bool:
+    """common.h Divider: frexpf(d) == +-0.5 -- the divisor's fp32 value is a power of two of either sign (x / d is then x * (1 / d), exact)."""
+    m, _ = math.frexp(float(np.float32(div_fac)))
+    return abs(m) == 0.5
+
+
+def _perlin_parts(seed, stream, terms, chw, div_fac, n, elem_offset, first, count):
+    chw, n = int(chw), int(n)
+    count = n - int(first) if count is None else int(count)
+    assert 0 <= first and first + count <= n
+    t = np.zeros((0, chw)) if terms is None else np.asarray(terms)
+    t = np.zeros((0, chw)) if t.size == 0 else t.reshape(1, -1) if t.ndim == 1 else t.reshape(t.shape[0], -1)
+    assert t.shape[1] == chw, "a term table is one latent"
+    u = _tile_values(seed, stream, count, int(elem_offset) + int(first), u01)  # (u01 of stream_words, tile chunks at a time)
+    pos = (np.arange(int(first), int(first) + count, dtype=np.int64)) % chw
+    return u, t, pos
+
+
+def perlin_values(seed: int, stream: int, terms, chw: int, div_fac: float, n: int, elem_offset: int = 0, first: int = 0, count=None):
+    """sonar_perlin_generate_f32's values for the output indices first .. first + count - 1 (default: all) of a call of ``n`` elements whose
+    first element is the global element ``elem_offset``: u01(stream word of elem_offset + i) / div_fac + sum_t terms[t][i % chw], with
+    ``terms`` [iters, chw] or [chw] (iters = 0: no table) and ``div_fac`` rounded to fp32 as the C ABI takes it.  Returns
+    (values fp64, float32_steps): float32_steps(fused=False) is the same sequence rounded as the kernels round it, in np.float32 --
+      power-of-two divisor: u / d is exact; the general route adds the tables in order, one rounding each; the fast route (one table) forms
+        the exact u / d + term and rounds once (``fused``: the same bits, u / d being exact);
+      any other divisor: fl(u / d), then the adds in table order, one rounding each -- with the division correctly rounded."""
+    u, t, pos = _perlin_parts(seed, stream, terms, chw, div_fac, n, elem_offset, first, count)
+    d32 = np.float32(div_fac)
+    d = float(d32)
+    value = u / d
+    for row in t:
+        value = value + row.astype(np.float64)[pos]
+
+    def float32_steps(fused: bool = False):
+        if fused and divisor_is_power_of_two(d32) and t.shape[0] == 1:
+            return (u / d + t[0].astype(np.float32).astype(np.float64)[pos]).astype(np.float32)  # exact in fp64 (24 + 24 bits), one rounding
+        v = u.astype(np.float32) / d32  # (numpy divides correctly rounded; exact for a power of two)
+        for row in t:
+            v = v + row.astype(np.float32)[pos]
+        return v
+
+    return value, float32_steps
+
+
+def perlin_rounding_bound(seed: int, stream: int, terms, chw: int, div_fac: float, n: int, elem_offset: int = 0, first: int = 0, count=None):
+    """Per value, the bound on |fp32 kernel - fp64 value| of perlin_values: (1 + 0.5 max(iters, 1)) spacing32(M), M the largest of |u / d|
+    and the running partial sums -- one ulp for the division, correctly rounded or not, and half an ulp per add."""
+    u, t, pos = _perlin_parts(seed, stream, terms, chw, div_fac, n, elem_offset, first, count)
+    run = u / float(np.float32(div_fac))
+    mag = np.abs(run)
+    for row in t:
+        run = run + row.astype(np.float64)[pos]
+        mag = np.maximum(mag, np.abs(run))
+    return (1.0 + 0.5 * max(t.shape[0], 1)) * np.spacing(mag.astype(np.float32)).astype(np.float64)
 
 
 # ------------------------------------------------------------------------------------------------ pyramid streams (noise_gen.hip: pyramid_plane_body, fill_levels, level_normal)

@@ -212,6 +212,72 @@ def test_pyramid_planes_of_a_shard_is_the_slice_of_the_whole():
     assert np.allclose(whole, want, rtol=0, atol=1e-13)
 
 
+# ------------------------------------------------------------------------------------------------ Perlin
+@pytest.mark.parametrize("blend_mode", ds.PERLIN_BLENDS)
+def test_perlin_lattice_is_the_reference_term_of_its_own_angles(blend_mode):
+    """perlin_lattice against oracle.sonar_oracle.perlin_term (the reference's cell-centre evaluation, torch fp64) of the angles
+    perlin_lattice_revolutions states, summed over the iterations; the draws by a scalar walk of the counter rule."""
+    import torch
+
+    from oracle import sonar_oracle as orc
+
+    seed, stream, iters, C, H, W = 2**32 + 5, 2**47 + 1, 6, 2, 5, 7
+    rev = ds.perlin_lattice_revolutions(seed, stream, iters, C, H, W)
+    assert rev.shape == (iters, C, H + 1, W + 1) and rev.min() >= 0.0 and rev.max() < 1.0
+    for it, c, gy, gx in ((0, 0, 0, 0), (3, 1, 5, 7), (4, 0, 2, 3), (5, 1, 0, 6)):
+        p = (c * (H + 1) + gy) * (W + 1) + gx
+        w = ds.philox4x32_10(p, 0, it // 4, stream & 0xFFFFFFFF, seed & 0xFFFFFFFF, seed >> 32)
+        assert rev[it, c, gy, gx] == ds.u01(w[it % 4])
+    want = sum(orc.perlin_term(torch.from_numpy(2.0 * math.pi * rev[it]), blend_mode) for it in range(iters)).numpy()
+    got = ds.perlin_lattice(seed, stream, iters, C, H, W, blend_mode)
+    assert got.shape == (C, H, W) and np.max(np.abs(got - want)) < 1e-14
+    assert np.array_equal(ds.perlin_lattice(seed, stream, 0, C, H, W, blend_mode), np.zeros((C, H, W)))
+    # a prefix of the iterations is a prefix of the sum: iteration `it` does not depend on how many follow
+    assert np.allclose(ds.perlin_lattice(seed, stream, 5, C, H, W, blend_mode) + ds.perlin_cell_terms(rev[5], blend_mode), got, rtol=0, atol=1e-14)
+
+
+def test_perlin_lattice_takes_the_low_word_of_the_stream_id():
+    a = ds.perlin_lattice_revolutions(7, 3, 5, 1, 3, 4)
+    assert np.array_equal(a, ds.perlin_lattice_revolutions(7, 2**32 + 3, 5, 1, 3, 4))
+    assert np.all(a != ds.perlin_lattice_revolutions(7, 4, 5, 1, 3, 4)) and np.all(a != ds.perlin_lattice_revolutions(2**32 + 7, 3, 5, 1, 3, 4))
+
+
+def test_perlin_values_windows_are_slices_of_the_whole_call():
+    seed, stream, chw, B, off = 2**64 - 1, 2**32 + 3, 260, 40, 3 * 260
+    n = B * chw
+    terms = np.random.default_rng(2).standard_normal((2, chw)).astype(np.float32)
+    whole, steps = ds.perlin_values(seed, stream, terms, chw, 1.5, n, off)
+    u = ds.uniform_fill(seed, stream, n, off).astype(np.float64)
+    pos = np.arange(n) % chw
+    assert np.array_equal(whole, u / float(np.float32(1.5)) + terms[0].astype(np.float64)[pos] + terms[1].astype(np.float64)[pos])
+    for first, count in ((0, 1), (4095, 2), (4096 - off, 4096), (n - 5, 5), (777, 3000)):
+        part, psteps = ds.perlin_values(seed, stream, terms, chw, 1.5, n, off, first, count)
+        assert np.array_equal(part, whole[first:first + count]) and np.array_equal(psteps(), steps()[first:first + count])
+    # a shard is the slice of the batch: the tables repeat per latent, the words follow the global element
+    shard, _ = ds.perlin_values(seed, stream, terms, chw, 1.5, 10 * chw, off + 7 * chw)
+    assert np.array_equal(shard, whole[7 * chw:17 * chw])
+    # one table given flat, and none at all
+    one, _ = ds.perlin_values(seed, stream, terms[0], chw, 2.0, n, off)
+    assert np.array_equal(one, u / 2.0 + terms[0].astype(np.float64)[pos])
+    none, nsteps = ds.perlin_values(seed, stream, np.zeros((0, chw), np.float32), chw, -4.0, n, off)
+    assert np.array_equal(none, u / -4.0) and np.array_equal(nsteps().astype(np.float64), none)
+
+
+@pytest.mark.parametrize("div_fac", [2.0, 0.5, 1.0, -4.0, 1.5, 3.0, -1.7])
+def test_perlin_float32_steps_stay_within_the_rounding_bound(div_fac):
+    seed, stream, chw, n = 5, 2**47 + 1, 1024, 3 * 1024
+    rng = np.random.default_rng(11)
+    assert ds.divisor_is_power_of_two(div_fac) == (div_fac in (2.0, 0.5, 1.0, -4.0))
+    for terms in (rng.standard_normal((1, chw)).astype(np.float32), rng.standard_normal((3, chw)).astype(np.float32), np.zeros((0, chw), np.float32)):
+        value, steps = ds.perlin_values(seed, stream, terms, chw, div_fac, n, 64)
+        bound = ds.perlin_rounding_bound(seed, stream, terms, chw, div_fac, n, 64)
+        got = steps()
+        assert got.dtype == np.float32 and np.all(np.abs(got.astype(np.float64) - value) <= bound)
+        assert np.max(np.abs(got.astype(np.float64) - value)) < 2e-6  # (the bound is a few ulps of values of size ~3, not a loose one)
+        if terms.shape[0] == 1:
+            assert np.array_equal(steps(fused=True), got)  # a power of two: one rounding of the exact sum is the rounded steps' bits
+
+
 # ------------------------------------------------------------------------------------------------ half-spectrum draw orders
 @pytest.mark.parametrize("shape", list(ds.FIXED_PLANES) + [(104, 152), (96, 168), (256, 256)])
 def test_every_half_spectrum_element_is_drawn_once(shape):
