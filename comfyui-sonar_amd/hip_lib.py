@@ -27,7 +27,7 @@ UPSCALE_MODES = ("bilinear", "nearest-exact", "area", "adaptive_avg_pool2d", "ne
 PYRAMID_FUSED_MODES = ("bilinear", "nearest-exact", "area", "adaptive_avg_pool2d")                  # modes the fused pyramid kernels carry
 DWT_MODE_IDS = {"zero": 0, "symmetric": 1, "reflect": 2, "periodization": 3, "periodic": 4, "constant": 5, "replicate": 5}
 NPART = 1024
-BROWNIAN_MAX_TERMS = 96  # kMaxBrownianNodes (csrc/noise_gen.hip)
+BROWNIAN_MAX_TERMS = 96  # kMaxBrownianNodes (csrc/noise_brownian.hip)
 ERR_ARG, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3  # include/sonar_hip.h
 DTYPE_IDS = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}  # SONAR_DTYPE_* (the entry points that take a dtype code)
 CFG_BLEND_NONE = -1  # SONAR_CFG_BLEND_NONE

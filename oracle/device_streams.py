@@ -46,10 +46,10 @@ MWC_A = 4294883355
 
 TILE_ITERS = 16                  # common.h kTileIters
 TILE_ELEMS = TILE_ITERS * 256    # common.h kTileElems: 16 steps x 64 lanes x 4 slots
-BROWN_ITERS = 4                  # noise_gen.hip kBrownIters
-BROWN_TILE = BROWN_ITERS * 256   # noise_gen.hip kBrownTile
-BROWN_STREAM = 0xB0B000000001    # noise_gen.hip kBrownStream
-BROWNIAN_MAX_NODES = 96          # noise_gen.hip kMaxBrownianNodes
+BROWN_ITERS = 4                  # noise_brownian.hip kBrownIters
+BROWN_TILE = BROWN_ITERS * 256   # noise_brownian.hip kBrownTile
+BROWN_STREAM = 0xB0B000000001    # noise_brownian.hip kBrownStream
+BROWNIAN_MAX_NODES = 96          # noise_brownian.hip kMaxBrownianNodes
 
 
 def _u64(v):
@@ -149,7 +149,7 @@ def angle_hi(w):
     return (_u64(w) >> np.uint64(16)).astype(np.float64) * 2.0**-16
 
 
-# ------------------------------------------------------------------------------------------------ the tile walk (common.h:144-147, noise_gen.hip:27-42)
+# ------------------------------------------------------------------------------------------------ the tile walk (common.h kTileIters / kTileElems, noise_stream.h for_each_group)
 def tile_position(e):
     """Global element e -> (tile, lane, step, slot): tile e // 4096, lane (e % 256) // 4, burst step (e % 4096) // 256, slot e % 4.
     One step of a lane takes four words, one per slot."""
@@ -216,7 +216,7 @@ def philox_normal4(seed: int, stream: int, group):
     return _normal4(np.stack(w, axis=-1))
 
 
-# ------------------------------------------------------------------------------------------------ Perlin (noise_gen.hip: perlin_lattice_cells, perlin_generate_kernel, perlin_fast_tiles; common.h Divider)
+# ------------------------------------------------------------------------------------------------ Perlin (noise_stream.h perlin_lattice_cells; noise_perlin.hip perlin_generate_kernel, perlin_fast_tiles; common.h Divider)
 PERLIN_BLENDS = ("lerp", "inject", "subtract_b")  # common.h blend, SONAR_BLEND_* 0 / 1 / 2
 
 
@@ -322,9 +322,9 @@ def perlin_rounding_bound(seed: int, stream: int, terms, chw: int, div_fac: floa
     return (1.0 + 0.5 * max(t.shape[0], 1)) * np.spacing(mag.astype(np.float32)).astype(np.float64)
 
 
-# ------------------------------------------------------------------------------------------------ pyramid streams (noise_gen.hip: pyramid_plane_body, fill_levels, level_normal)
-PYRAMID_SLOTS = 256        # noise_gen.hip kBlock: generator slots of one drawn level grid
-PYRAMID_MAX_LEVELS = 12    # noise_gen.hip kMaxLevels
+# ------------------------------------------------------------------------------------------------ pyramid streams (noise_pyramid.hip: pyramid_plane_body, fill_levels, level_normal)
+PYRAMID_SLOTS = 256        # common.h kBlock: generator slots of one drawn level grid
+PYRAMID_MAX_LEVELS = 12    # noise_pyramid.hip kMaxLevels
 
 
 def pyramid_level_grid(seed: int, stream_id: int, level_index: int, plane: int, h: int, w: int):
@@ -342,7 +342,7 @@ def pyramid_level_grid(seed: int, stream_id: int, level_index: int, plane: int, 
 
 
 def level_normal(seed: int, stream: int, e):
-    """noise_gen.hip level_normal: the level value at the global element index e = (plane_offset + p) h w + y w + x is slot e % 4 of
+    """noise_pyramid.hip level_normal: the level value at the global element index e = (plane_offset + p) h w + y w + x is slot e % 4 of
     philox_normal4(seed, stream, e // 4).  Level l of a sonar_levels_sampled_f32 call uses the stream id stream_id + l."""
     e = np.asarray(e, dtype=np.int64)
     z = philox_normal4(seed, int(stream) & (2**64 - 1), (e // 4).astype(np.uint64))
@@ -385,7 +385,7 @@ def pyramid_planes(seed: int, stream_id: int, planes: int, H: int, W: int, level
     return (out, mag) if magnitude else out
 
 
-# ------------------------------------------------------------------------------------------------ Brownian z(node, e) (noise_gen.hip:1980-2180, 2296-2321)
+# ------------------------------------------------------------------------------------------------ Brownian z(node, e) (noise_brownian.hip: brownian_burst_kernel, brownian_burst_add, brownian_kernel, brownian_launch)
 def splitmix64(v) -> int:
     """splitmix64 finaliser of v (brownian_launch: the node id's (hx, hc) = low / high word)."""
     h = (int(v) + 0x9E3779B97F4A7C15) & (2**64 - 1)

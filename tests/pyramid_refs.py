@@ -119,7 +119,7 @@ def resize(grids, H: int, W: int, mode: str, fused: bool = False):
     return np.einsum("yi,...ij,xj->...yx", axis_matrix(h, H, mode, fused), g, axis_matrix(w, W, mode, fused), optimize=True)
 
 
-# ------------------------------------------------------------------------------------------------ the route (noise_gen.hip pyramid_route)
+# ------------------------------------------------------------------------------------------------ the route (noise_pyramid.hip pyramid_route)
 LDS_BUDGET = 64 * 1024   # kPyramidLdsBudget
 LIN_BYTES = 16           # sizeof(Lin): one coordinate-table entry
 FLAT, PLANE, STRETCHED = 0, 1, 2
