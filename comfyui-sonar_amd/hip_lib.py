@@ -201,6 +201,8 @@ SIGNATURES = {
     "sonar_group_scale_noise_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _F, _P]),
     "sonar_shuffle_gather_f32": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _I, _P, _I, _P]),
     "sonar_shuffle_generate_f32": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _I, _F, _I, _U64, _U64, _I64, _P]),
+    "sonar_collatz_chain_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _D, _D, _D, _D, _D, _D, _I, _I, _I, _P]),
+    "sonar_collatz_mix_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _I64, _I64, _F, _P]),
     "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
@@ -1906,6 +1908,53 @@ def shuffle_generate(x: torch.Tensor, dim: int, prob: float, no_identity: bool, 
     _check(load().sonar_shuffle_generate_f32(_dev(x, "x"), _dev(out, "out"), *_shuffle_shape(x, dim), float(prob), int(bool(no_identity)),
                                              seed & (2**64 - 1), int(stream_id), int(row_offset), _stream()), "sonar_shuffle_generate_f32")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ Collatz chains (csrc/collatz.hip)
+COLLATZ_INTEGER_MATH, COLLATZ_BREAK_LOOPS, COLLATZ_KEEP_SIGN = 1, 2, 4           # SONAR_COLLATZ_* flags
+COLLATZ_SEED_MODES = {"default": 0, "force_odd": 1, "force_even": 2}              # SONAR_COLLATZ_SEED_*
+COLLATZ_OUTPUTS = {"ratios": 0, "mults": 1, "adds": 2}                            # SONAR_COLLATZ_OUT_*
+COLLATZ_SECOND = {"one": 0, "seeds": 1, "mix": 2}                                 # SONAR_COLLATZ_SECOND_*
+
+
+def collatz_view(outer: int, length: int, inner: int, chain_length: int):
+    """(cl, n_chunks, len_p) of the kernels' view [outer][len][inner]: values kept per chain, chains along ``len``, padded length."""
+    cl = min(int(length), int(chain_length))
+    n_chunks = -(-int(length) // cl) if cl > 0 else 0
+    return cl, n_chunks, n_chunks * cl
+
+
+def collatz_chain(seeds: torch.Tensor, seed_ext: torch.Tensor, outer: int, length: int, inner: int, chain_length: int, chain_offset: int, *,
+                  span: float, rmin: float, even_multiplier: float, even_addition: float, odd_multiplier: float, odd_addition: float,
+                  integer_math: bool, break_loops: bool, add_preserves_sign: bool, seed_mode: str, output: str,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sonar_collatz_chain_f32: the chains of one iteration from their ``seeds`` [outer][n_chunks][inner]; ``seed_ext`` is the device
+    scalar whose start value is the largest.  Returns the kept values in the padded layout, flat: [outer * len_p * inner]."""
+    cl, n_chunks, len_p = collatz_view(outer, length, inner, chain_length)
+    if seeds.numel() != outer * n_chunks * inner:
+        raise SonarHipError(f"collatz_chain: {seeds.numel()} seeds for {outer} x {n_chunks} x {inner} chains")
+    out = torch.empty(outer * len_p * inner, dtype=torch.float32, device=seeds.device) if out is None else out
+    if out.numel() != outer * len_p * inner:
+        raise SonarHipError(f"collatz_chain: out holds {out.numel()} values, the padded layout {outer * len_p * inner}")
+    flags = (COLLATZ_INTEGER_MATH if integer_math else 0) | (COLLATZ_BREAK_LOOPS if break_loops else 0) | (COLLATZ_KEEP_SIGN if add_preserves_sign else 0)
+    _check(load().sonar_collatz_chain_f32(_dev(seeds, "seeds"), _dev(seed_ext, "seed_ext"), _dev(out, "out"), int(outer), int(length), int(inner),
+                                          int(chain_length), int(chain_offset), float(span), float(rmin), float(even_multiplier),
+                                          float(even_addition), float(odd_multiplier), float(odd_addition), flags,
+                                          COLLATZ_SEED_MODES[seed_mode], COLLATZ_OUTPUTS[output], _stream()), "sonar_collatz_chain_f32")
+    return out
+
+
+def collatz_mix_(acc: torch.Tensor, out1: torch.Tensor, second: Optional[torch.Tensor], second_mode: str, outer: int, length: int, inner: int,
+                 chain_length: int, scale: float) -> torch.Tensor:
+    """sonar_collatz_mix_f32: ``acc`` [outer][len][inner] += (out1 * second) * scale, ``out1`` in the padded layout; in place."""
+    cl, n_chunks, len_p = collatz_view(outer, length, inner, chain_length)
+    if acc.numel() != outer * length * inner or out1.numel() != outer * len_p * inner:
+        raise SonarHipError(f"collatz_mix_: acc of {acc.numel()} and out1 of {out1.numel()} values for the view {outer} x {length} x {inner}")
+    if second is not None and second.numel() != (outer * n_chunks * inner if second_mode == "seeds" else acc.numel()):
+        raise SonarHipError(f"collatz_mix_: a second factor of {second.numel()} values for mode {second_mode!r}")
+    _check(load().sonar_collatz_mix_f32(_dev(acc, "acc"), _dev(out1, "out1"), _opt(second, "second"), COLLATZ_SECOND[second_mode], int(outer),
+                                        int(length), int(inner), int(chain_length), float(scale), _stream()), "sonar_collatz_mix_f32")
+    return acc
 
 
 IMAGE_BLEND_IDS = BLEND_IDS | {"simple_add": 3}  # SONAR_IMAGE_BLEND_ADD

@@ -24,6 +24,7 @@ from .noise_generation import (
     current_batch_offset,
     BrownianNoiseGenerator,
     CollatzNoiseGenerator,
+    CollatzOffPath,
     DistroNoiseGenerator,
     GaussianNoiseGenerator,
     GreenTestNoiseGenerator,
@@ -460,6 +461,27 @@ class AdvancedDistroNoise(AdvancedNoiseBase):
     @property
     def ns_factory(self):
         return DistroNoiseGenerator
+
+
+class AdvancedCollatzNoise(AdvancedNoiseBase):
+    """py/noise.py:332-389: CollatzNoiseGenerator with an optional chain for the seeds and, in the ``noise_*`` output modes, one for the
+    mix noise; both are sampled un-normalised.  The reference hands only the positional arguments on to the generator; here ``cpu`` chooses
+    between replay and generate mode, so the keyword arguments go on as well."""
+
+    ns_factory_arg_keys = ("adjust_scale", "iteration_sign_flipping", "chain_length", "iterations", "rmin", "rmax", "flatten", "dims",
+                           "output_mode", "noise_dtype", "quantile", "quantile_strategy", "integer_math", "add_preserves_sign",
+                           "even_multiplier", "even_addition", "odd_multiplier", "odd_addition", "chain_offset", "seed_mode", "break_loops")
+
+    @property
+    def ns_factory(self):
+        return CollatzNoiseGenerator
+
+    def make_noise_sampler(self, x, *args, normalized=True, **kwargs):
+        seed_chain, mix_chain = getattr(self, "seed_custom_noise", None), getattr(self, "mix_custom_noise", None)
+        seed_ns = seed_chain.make_noise_sampler(x, *args, normalized=False, **kwargs) if seed_chain is not None else None
+        mix_ns = (mix_chain.make_noise_sampler(x, *args, normalized=False, **kwargs)
+                  if mix_chain is not None and self.output_mode.startswith("noise_") else None)
+        return super().make_noise_sampler(x, *args, normalized=normalized, seed_noise_sampler=seed_ns, mix_noise_sampler=mix_ns, **kwargs)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1503,7 +1525,7 @@ NOISE_SAMPLERS: dict[NoiseType, Callable] = {
                                     output=_scaled(1.15)),
     NoiseType.GREEN_TEST: NoiseSampler.wrap(GreenTestNoiseGenerator),
     NoiseType.POWER_OLD: NoiseSampler.wrap(PowerOldNoiseGenerator),
-    NoiseType.COLLATZ: NoiseSampler.wrap(CollatzNoiseGenerator),
+    NoiseType.COLLATZ: NoiseSampler.wrap(CollatzOffPath),  # the type keeps refusing; AdvancedCollatzNoise is the way in
     NoiseType.PYRAMID_OLD: NoiseSampler.wrap(PyramidOldNoiseGenerator),
     NoiseType.PYRAMID_BISLERP: NoiseSampler.wrap(partial(PyramidNoiseGenerator, upscale_mode="bislerp")),
     NoiseType.HIGHRES_PYRAMID_BISLERP: NoiseSampler.wrap(partial(HighresPyramidNoiseGenerator, upscale_mode="bislerp")),

@@ -851,8 +851,105 @@ def _off_path(type_name: str):
 
 
 VoronoiNoiseGenerator = _off_path("voronoi")
-CollatzNoiseGenerator = _off_path("collatz")
+CollatzOffPath = _off_path("collatz")  # what NoiseType.COLLATZ and its node keep pointing at: the registry is unchanged
 ScatternetFilteredNoiseGenerator = _off_path("scatternet_filtered")
+
+
+class CollatzNoiseGenerator(NoiseGenerator):
+    """py/noise_generation.py:2330-2615.  Every iteration is two launches around the pinned helpers: the chain kernel (csrc/collatz.hip; the
+    start values, the recurrence and the kept output of every chain, straight into the trimmed padded layout), utils.quantile_normalize on
+    that padded tensor, and the mix-accumulate kernel into one fp32 accumulator.  The seeds (and the mix noise of the ``noise_x_*`` modes,
+    after them) come from ``rand_like``: the host generator in replay mode, one Philox stream per draw in generate mode -- iteration k of a
+    call takes stream + k, or stream + 2k and + 2k + 1 with a drawn mix noise.  float32 only.  The zero replacement uses the max and the
+    count of the seeds this call sees: under ``shard_offset`` the shard's, not the whole batch's."""
+
+    name = "collatz"
+    OUTPUT_MODES = {"values": ("ratios", "seeds"), "ratios": ("ratios", "one"), "mults": ("mults", "one"), "adds": ("adds", "one"),
+                    "seed_x_ratios": ("ratios", "seeds"), "seed_x_mults": ("mults", "seeds"), "seed_x_adds": ("adds", "seeds"),
+                    "noise_x_ratios": ("ratios", "mix"), "noise_x_mults": ("mults", "mix"), "noise_x_adds": ("adds", "mix")}
+
+    @classmethod
+    def ng_params(cls):
+        return super().ng_params() | {
+            "adjust_scale": False, "iteration_sign_flipping": True, "chain_length": (1, 1, 2, 2, 3, 3), "iterations": 10,
+            "rmin": -8000.0, "rmax": 8000.0, "flatten": False, "dims": (-1, -1, -2, -2), "output_mode": "values", "quantile": 0.5,
+            "quantile_strategy": "clamp", "noise_dtype": torch.float32, "integer_math": True, "even_multiplier": 0.5,
+            "even_addition": 0.0, "odd_multiplier": 3.0, "odd_addition": 1.0, "add_preserves_sign": True, "chain_offset": 5,
+            "break_loops": True, "seed_mode": "default", "seed_noise_sampler": None, "mix_noise_sampler": None,
+        }
+
+    def _refusals(self) -> tuple:
+        """Everything that stops a call, before anything is drawn or launched.  Returns the normalised dims."""
+        if self.noise_dtype not in (torch.float32, "float32"):
+            raise NotImplementedError(f"CollatzNoiseGenerator: noise_dtype {self.noise_dtype} is not supported by this build (the chain "
+                                      "kernels compute in float32)")
+        out_dims = len(self.shape)
+        dims = tuple(dim if dim >= 0 else out_dims + dim for dim in self.dims)
+        if not all(0 <= d < out_dims for d in dims):
+            raise ValueError("Dimension out of range")
+        if self.output_mode not in self.OUTPUT_MODES:
+            raise ValueError("Bad output mode")
+        if self.seed_mode not in hip_lib.COLLATZ_SEED_MODES:
+            raise ValueError("Bad seed mode")
+        if current_batch_offset() != 0 and (self.quantile not in {0, 1} or 0 in dims):
+            raise NotImplementedError("CollatzNoiseGenerator: quantile normalisation and chains along dim 0 reduce across the samples of the "
+                                      "batch, which a sharded batch splits (generate on one rank, or use per-sample dims with quantile 0 or 1)")
+        return dims
+
+    def _seeds(self, args, dim: int, flatten: bool, chunk_shape: list) -> Tensor:
+        """The uniforms of one iteration's chains, or the seed sampler's noise cropped, flattened and rescaled in the reference's order."""
+        if self.seed_noise_sampler is None:
+            return self.rand_like(fun=torch.rand, shape=chunk_shape, dtype=torch.float32).contiguous()
+        crop = tuple(slice(None, sz) for sz in chunk_shape)
+        noise = self.seed_noise_sampler(*args)
+        utils.pop_stats(noise)
+        noise = noise[crop].to(device=self.device, dtype=torch.float32)
+        if flatten:
+            noise = noise.flatten(start_dim=dim)
+        noise = noise[crop].contiguous()
+        if list(noise.shape) != list(chunk_shape):
+            raise ValueError(f"seed_noise_sampler: noise of shape {tuple(noise.shape)} does not cover the chains {tuple(chunk_shape)}")
+        return utils.normalize_to_scale(noise, 1e-06, 1.0, dim=tuple(range(1, len(chunk_shape)))).contiguous()
+
+    def _iteration(self, args, acc: Tensor, dim: int, chain_length: int, scale: float) -> None:
+        shape = tuple(self.shape)
+        flatten = bool(self.flatten)
+        outer = math.prod(shape[:dim])
+        length = math.prod(shape[dim:]) if flatten else shape[dim]
+        inner = 1 if flatten else math.prod(shape[dim + 1:])
+        cl, n_chunks, _len_p = hip_lib.collatz_view(outer, length, inner, chain_length)
+        chunk_shape = [*shape[:dim], n_chunks] if flatten else [*shape[:dim], n_chunks, *shape[dim + 1:]]
+        seeds = self._seeds(args, dim, flatten, chunk_shape)
+        span = self.rmax - self.rmin + 1
+        lo, hi = hip_lib.minmax_rows(seeds, 1, seeds.numel())  # the start value is monotonic in the seed: its max is the extreme seed's
+        kept, second = self.OUTPUT_MODES[self.output_mode]
+        out1 = hip_lib.collatz_chain(seeds, hi if span >= 0 else lo, outer, length, inner, chain_length, self.chain_offset, span=span,
+                                     rmin=self.rmin, even_multiplier=self.even_multiplier, even_addition=self.even_addition,
+                                     odd_multiplier=self.odd_multiplier, odd_addition=self.odd_addition, integer_math=self.integer_math,
+                                     break_loops=self.break_loops, add_preserves_sign=self.add_preserves_sign, seed_mode=self.seed_mode,
+                                     output=kept)
+        if self.quantile not in {0, 1}:
+            out1 = utils.quantile_normalize(out1, quantile=self.quantile, dim=0, strategy=self.quantile_strategy).contiguous()
+        mix = None
+        if second == "mix":
+            mix = self.rand_like(dtype=torch.float32) if self.mix_noise_sampler is None else self.mix_noise_sampler(*args)
+            utils.pop_stats(mix)
+            mix = utils.as_f32(mix.to(self.device))
+            if mix.numel() != acc.numel():
+                raise ValueError(f"mix_noise_sampler: noise of shape {tuple(mix.shape)} for a latent of shape {shape}")
+        hip_lib.collatz_mix_(acc, out1, seeds if second == "seeds" else mix, second, outer, length, inner, chain_length, scale)
+
+    def generate(self, *args):
+        dims = self._refusals()
+        n_dims, n_chainlens = len(dims), len(self.chain_length)
+        result = torch.zeros(tuple(self.shape), dtype=torch.float32, device=self.device)
+        it_scale = 1.0 / self.iterations
+        for iteration in range(self.iterations):
+            sign = -1 if self.iteration_sign_flipping and (iteration & 1) == 1 else 1
+            self._iteration(args, result, dims[iteration % n_dims], self.chain_length[iteration % n_chainlens], it_scale * sign)
+        if self.adjust_scale:
+            result = utils.normalize_to_scale(result, -1.0, 1.0, dim=tuple(range(1 if result.ndim < 4 else 2, result.ndim)))
+        return result
 
 
 def _lowrank_mvn(loc, cov_factor, cov_diag):

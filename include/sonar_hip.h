@@ -431,6 +431,39 @@ int sonar_shuffle_gather_f32(const float* src, float* out, int ndim, int64_t s0,
 int sonar_shuffle_generate_f32(const float* src, float* out, int ndim, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t s4, int dim,
                                float prob, int no_identity, uint64_t seed, uint64_t stream_id, int64_t row_offset, void* stream);
 
+/* ---------------------------------------------------------------- CollatzNoiseGenerator */
+/* One iteration of CollatzNoiseGenerator (py/noise_generation.py:2330-2615) over the view [outer][len][inner] of a contiguous fp32 latent
+ * (not flattened: len = the size of `dim`, inner = the product of the sizes behind it; flattened: len = the product from `dim` on,
+ * inner = 1).  cl = min(len, chain_length), n_chunks = ceil(len / cl), chains = outer * n_chunks * inner, len_p = n_chunks * cl.
+ *  sonar_collatz_chain_f32  seeds [outer][n_chunks][inner] -> out [outer][len_p][inner].  Per chain: noise = seed * span + rmin (the scalars
+ *                           rounded to fp32), an exact zero replaced by (*seed_ext * span + rmin) / chains -- seed_ext a device scalar, the
+ *                           seed that gives the largest noise (the largest seed for span >= 0, else the smallest), so the value is
+ *                           noise.max() / noise.numel() without a read on the host -- then the seed_mode parity fix and cl + chain_offset
+ *                           links of the recurrence in registers.  Kept per link past chain_offset: result / noise (OUT_RATIOS), muls
+ *                           (OUT_MULTS) or adds / noise (OUT_ADDS).  The shortcuts for even / odd multipliers of 1 and additions of 0 are
+ *                           decided on the doubles as given.  Every step is one correctly rounded fp32 operation.
+ *  sonar_collatz_mix_f32    acc[o][j][i] += (out1[o][j][i] * second) * scale for j < len (out1 in the padded layout); second is 1
+ *                           (SECOND_ONE, `second` may be NULL), seeds[o][j / cl][i] (SECOND_SEEDS) or second[o][j][i] (SECOND_MIX).
+ * SONAR_ERR_ARG: a NULL pointer, out == seeds (acc == an input), a negative size or one beyond 2^31, chain_length < 1, chain_offset < 0,
+ * more than 2^31 chains, an unknown flag, mode or output.  All checked before anything is launched; an empty view launches nothing. */
+#define SONAR_COLLATZ_INTEGER_MATH 1
+#define SONAR_COLLATZ_BREAK_LOOPS 2
+#define SONAR_COLLATZ_KEEP_SIGN 4
+#define SONAR_COLLATZ_SEED_DEFAULT 0
+#define SONAR_COLLATZ_SEED_FORCE_ODD 1
+#define SONAR_COLLATZ_SEED_FORCE_EVEN 2
+#define SONAR_COLLATZ_OUT_RATIOS 0
+#define SONAR_COLLATZ_OUT_MULTS 1
+#define SONAR_COLLATZ_OUT_ADDS 2
+#define SONAR_COLLATZ_SECOND_ONE 0
+#define SONAR_COLLATZ_SECOND_SEEDS 1
+#define SONAR_COLLATZ_SECOND_MIX 2
+int sonar_collatz_chain_f32(const float* seeds, const float* seed_ext, float* out, int64_t outer, int64_t len, int64_t inner,
+                            int64_t chain_length, int64_t chain_offset, double span, double rmin, double emul, double eadd, double omul,
+                            double oadd, int flags, int seed_mode, int output, void* stream);
+int sonar_collatz_mix_f32(float* acc, const float* out1, const float* second, int second_mode, int64_t outer, int64_t len, int64_t inner,
+                          int64_t chain_length, float scale, void* stream);
+
 /* A pending global normalisation of a noise tensor (py/utils.py:100-105): the decision scale_noise(normalized=True) would take,
  * computed ON THE DEVICE from the tensor's (sum, sumsq) partials and left in device memory, so that the kernel that consumes the
  * noise (the sampler-step kernels below take it as `noise_norm`, nullable) applies `((v - mean) / std) * factor` -- only the parts
