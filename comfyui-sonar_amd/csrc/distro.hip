@@ -1,7 +1,8 @@
 // Distro noise, generate mode (DistroNoiseGenerator, py/noise_generation.py:805-1256): one fp32 value per output element, the selected
 // component of one draw of a torch.distributions family.  Each element owns its Philox4x32-10 blocks (counter = element index, block
 // number): values do not depend on the launch geometry or on how a batch is sharded.  Block allotment and word conversions are the
-// stream contract of INTEGRATION.md 3b; tests/test_gpu_distro.py restates the fixed-word families in numpy.
+// stream contract of INTEGRATION.md 3b; tests/test_gpu_distro.py restates the fixed-word families in numpy and tests/distro_refs.py the
+// rejection-sampled ones (gamma_draw, poisson_draw, vonmises_draw), proposal by proposal, in fp64.
 #include <float.h>
 #include <math.h>
 
@@ -61,7 +62,8 @@ __device__ __forceinline__ float gamma_draw(const DistroKey& key, uint32_t slot,
 }
 
 // Poisson: inversion of one uniform below rate 10 (the CDF summed in double), Hoermann's PTRS above (proposal j: block j, words 0 and 1;
-// after kMaxProposals rejections floor(rate)).
+// after kMaxProposals rejections floor(rate)).  k and the slow-path inequality are formed in double: both add terms of the size of
+// rate log(rate) to terms of size 1, which fp32 loses from rate ~1e3 up (the pmf fails a chi-square at 1e5).  The squeeze stays fp32.
 __device__ __forceinline__ float poisson_draw(const DistroKey& key, float rate) {
     if (rate < 10.0f) {
         const double u = (double)u_half(key.block(0).v[0]);
@@ -73,33 +75,39 @@ __device__ __forceinline__ float poisson_draw(const DistroKey& key, float rate) 
         }
         return (float)k;
     }
-    const float slam = sqrtf(rate), loglam = logf(rate);
+    const float slam = sqrtf(rate);
+    const double drate = (double)rate, dloglam = log(drate);
     const float b = 0.931f + 2.53f * slam, a = -0.059f + 0.02483f * b;
     const float inv_alpha = 1.1239f + 1.1328f / (b - 3.4f), vr = 0.9277f - 3.6224f / (b - 2.0f);
     for (int j = 0; j < kMaxProposals; ++j) {
         const Philox4 p = key.block(j);
         const float U = u_open(p.v[0]) - 0.5f, V = u_open(p.v[1]);
         const float us = 0.5f - fabsf(U);
-        const float k = floorf((2.0f * a / us + b) * U + rate + 0.43f);
+        const float k = (float)floor((double)((2.0f * a / us + b) * U) + drate + 0.43);
         if (us >= 0.07f && V <= vr) return k;
         if (k < 0.0f || (us < 0.013f && V > us)) continue;
-        if (logf(V) + logf(inv_alpha) - logf(a / (us * us) + b) <= -rate + k * loglam - lgammaf(k + 1.0f)) return k;
+        if ((double)(logf(V) + logf(inv_alpha) - logf(a / (us * us) + b)) <= -drate + (double)k * dloglam - lgamma((double)k + 1.0)) return k;
     }
     return floorf(rate);
 }
 
 // von Mises (Best-Fisher, torch's _rejection_sample): proposal j takes block j, words 0-2; wrapped to [-pi, pi) as torch does.  After
-// kMaxProposals rejections the offset from loc is 0 (the mode).
-__device__ __forceinline__ float vonmises_draw(const DistroKey& key, float loc, float conc, float r) {
+// kMaxProposals rejections the offset from loc is 0 (the mode).  With z = cos(pi u) and f = (1 + r z) / (r + z), torch's c = conc (r - f)
+// and acos(f) cancel for large conc (r - 1 ~ 1 / (2 conc)) and acos loses half its digits at both ends.  The host passes rm1 = r - 1 from
+// double and everything is formed from 1 - z = 2 sin^2(pi u / 2) and 1 + z = 2 cos^2(pi u / 2): r + z = rm1 + (1 + z),
+// 1 - f = rm1 (1 - z) / (r + z), 1 + f = (r + 1) (1 + z) / (r + z), c = conc (rm1 + (1 - f)), angle = 2 atan2(sqrt(1 - f), sqrt(1 + f)).
+__device__ __forceinline__ float vonmises_draw(const DistroKey& key, float loc, float conc, float rm1) {
     float x = 0.0f;
     for (int j = 0; j < kMaxProposals; ++j) {
         const Philox4 p = key.block(j);
-        const float z = cospif(u_half(p.v[0]));
-        const float f = (1.0f + r * z) / (r + z);
-        const float c = conc * (r - f);
+        const float h = 0.5f * u_half(p.v[0]);  // [0, 1/2): the cosine stays positive
+        const float sh = sinpif(h), ch = cospif(h);
+        const float omz = 2.0f * sh * sh, opz = 2.0f * ch * ch;
+        const float omf = rm1 * omz / (rm1 + opz);
+        const float c = conc * (rm1 + omf);
         const float u2 = u_open(p.v[1]);
         if (c * (2.0f - c) - u2 > 0.0f || logf(c / u2) + 1.0f - c >= 0.0f) {
-            x = copysignf(acosf(f), u_half(p.v[2]) - 0.5f);
+            x = copysignf(2.0f * atan2f(sqrtf(rm1 * omz), sqrtf((rm1 + 2.0f) * opz)), u_half(p.v[2]) - 0.5f);
             break;
         }
     }

@@ -667,11 +667,15 @@ DISTRO_MAX_EVENT, DISTRO_MAX_PROPOSALS, DISTRO_DOMAIN = 16, 64, 0x44495354
 
 
 def distro_fill(shape, device, seed: int, stream_id: int, elem_offset: int, family: int, *, k: int = 0, row: int = 0, col: int = 0,
-                a: float = 0.0, b: float = 0.0, c: float = 0.0, v: Sequence[float] = ()) -> torch.Tensor:
-    """sonar_distro_fill_f32: a new tensor of ``shape``, every element the selected component of one draw of ``family``."""
+                a: float = 0.0, b: float = 0.0, c: float = 0.0, v: Sequence[float] = (), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sonar_distro_fill_f32: a new tensor of ``shape`` (or ``out``, fp32 of that shape), every element the selected component of one draw of
+    ``family``."""
     if len(v) > DISTRO_MAX_EVENT:
         raise SonarHipError(f"distro_fill: at most {DISTRO_MAX_EVENT} event parameters (got {len(v)})")
-    out = torch.empty(shape, dtype=torch.float32, device=device)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != tuple(shape) or out.dtype != torch.float32:
+        raise SonarHipError("distro_fill: out is not an fp32 tensor of the shape asked for")
     p = DistroParams(int(family), int(k), int(row), int(col), float(a), float(b), float(c), (C.c_float * 16)(*[float(x) for x in v]))
     _check(load().sonar_distro_fill_f32(_dev(out, "out"), out.numel(), seed & (2**64 - 1), int(stream_id), int(elem_offset), C.byref(p),
                                         _stream()),

@@ -1141,10 +1141,10 @@ class DistroNoiseGenerator(NoiseGenerator):
         elif fam == "uniform":
             p.update(a=f(dobj.low), b=f(dobj.high))
         elif fam == "vonmises":
-            kappa = f(dobj.concentration)  # torch's _proposal_r, in double
+            kappa = f(dobj.concentration)  # torch's _proposal_r less 1, in double: r - 1 = (1 - rho)^2 / (2 rho), about 1 / (2 kappa) when large
             tau = 1.0 + math.sqrt(1.0 + 4.0 * kappa * kappa)
             rho = (tau - math.sqrt(2.0 * tau)) / (2.0 * kappa)
-            p.update(a=f(dobj.loc), b=kappa, c=1.0 / kappa + kappa if kappa < 1e-5 else (1.0 + rho * rho) / (2.0 * rho))
+            p.update(a=f(dobj.loc), b=kappa, c=1.0 / kappa + kappa - 1.0 if kappa < 1e-5 else (1.0 - rho) ** 2 / (2.0 * rho))
         elif fam == "weibull":
             p.update(a=f(dobj.scale), b=f(dobj.concentration))
         elif fam == "wishart":

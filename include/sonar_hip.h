@@ -60,6 +60,8 @@ const char* sonar_last_error(void);
  *      seed and latents of a multiple of 4096 elements with the call on whole latents, one Philox4x32-10 block per 4 values (counter =
  *      (element / 4, node id), key = seed) for per-latent seeds and every other shape -- a function of the shape and the seed kind,
  *      never of buffer addresses (sonar_brownian_f32).
+ *   7: Distro noise's vonmises (formed from r - 1 and half-angle terms: no cancellation at large concentration) and poisson at rate >= 10
+ *      (k and the slow-path inequality in double); every other value is version 6's.
  * oracle/device_streams.py states every generate-mode stream in numpy; a change of values bumps this number and that file together. */
 int sonar_noise_stream_version(void);
 
@@ -198,7 +200,7 @@ int sonar_quantile_replace_apply_f32(const float* x, const float* stats, int64_t
  *   lkjcholesky (concentration; k = d; row, col)  lrmvariate_normal (loc, sqrt(cov_diag); v = cov_factor row, k = rank)
  *   mvariate_normal (loc, sqrt(cov_multiplier))  pareto (scale, alpha)  poisson (rate)  relaxed_bernoulli (logit, temperature)
  *   relaxed_onehotcategorical (temperature; v = logits, k, row = component)  studentt (loc, scale, df)  uniform (low, high)
- *   vonmises (loc, concentration, proposal_r)  weibull (scale, concentration)  wishart (df, cov_multiplier; k = d; row, col) */
+ *   vonmises (loc, concentration, proposal_r - 1)  weibull (scale, concentration)  wishart (df, cov_multiplier; k = d; row, col) */
 #define SONAR_DISTRO_EXPONENTIAL 0
 #define SONAR_DISTRO_CAUCHY 1
 #define SONAR_DISTRO_GEOMETRIC 2

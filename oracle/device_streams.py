@@ -37,7 +37,7 @@ import math
 
 import numpy as np
 
-STREAM_VERSION = 6
+STREAM_VERSION = 7
 
 U32 = np.uint64(0xFFFFFFFF)
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
