@@ -203,6 +203,11 @@ SIGNATURES = {
     "sonar_shuffle_generate_f32": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _I, _F, _I, _U64, _U64, _I64, _P]),
     "sonar_collatz_chain_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _D, _D, _D, _D, _D, _D, _I, _I, _I, _P]),
     "sonar_collatz_mix_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _I64, _I64, _F, _P]),
+    "sonar_voronoi_octave_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _F, _F, _I, _P, _P]),
+    "sonar_voronoi_fuzz_octave_f32": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _F, _F, _I, _P, _I, _I, _D, _U64, _U64, _I64, _P]),
+    "sonar_voronoi_gradient_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _F, _P]),
+    "sonar_voronoi_fuzz_add_f32": (_I, [_P, _P, _I64, _F, _F, _P]),
+    "sonar_voronoi_acc_f32": (_I, [_P, _P, _I64, _F, _F, _I, _P]),
     "sonar_image_channel_mean_f32": (_I, [_P, _I64, _I64, _I64, _P, _P]),
     "sonar_image_noise_compose_f32": (_I, [_P, _P, _P, _D, _D, _F, _F, _I, _I, _F, _U64, _P, _P, _I64, _I64, _I64, _I, _P, _P, _P]),
     "sonar_image_rescale_f32": (_I, [_P, _I64, _I64, _I64, _P, _P, _F, _P]),
@@ -1958,6 +1963,131 @@ def collatz_mix_(acc: torch.Tensor, out1: torch.Tensor, second: Optional[torch.T
         raise SonarHipError(f"collatz_mix_: a second factor of {second.numel()} values for mode {second_mode!r}")
     _check(load().sonar_collatz_mix_f32(_dev(acc, "acc"), _dev(out1, "out1"), _opt(second, "second"), COLLATZ_SECOND[second_mode], int(outer),
                                         int(length), int(inner), int(chain_length), float(scale), _stream()), "sonar_collatz_mix_f32")
+    return acc
+
+
+# ------------------------------------------------------------------------------------------------ Voronoi octaves (csrc/voronoi.hip)
+VORONOI_MAX_TERMS, VORONOI_MAX_CHAIN, VORONOI_MAX_POINTS, VORONOI_CHUNK = 4, 4, 4096, 256   # SONAR_VORONOI_MAX_* / _CHUNK
+VORONOI_FINAL_DIV = 1                                                                        # SONAR_VORONOI_FINAL_DIV
+VORONOI_METRICS = {"euclidean": 0, "manhatten": 1, "chebyshev": 2, "minkowski": 3, "quadratic": 4, "angle": 5, "angle_tanh": 6,
+                   "angle_sigmoid": 7}                                                      # SONAR_VORONOI_D_*
+VORONOI_XFORMS = {"weight": 0, "fractal_sin": 1, "fractal_cos": 2}                           # SONAR_VORONOI_X_*
+VORONOI_OPS = {"f": 0, "inv_f": 1, "diff": 2, "diff2": 3, "softmin": 4, "cellid": 5, "cellid_raw": 6}  # SONAR_VORONOI_R_*
+
+
+class VoronoiDTerm(C.Structure):
+    """sonar_voronoi_dterm"""
+    _fields_ = [("metric", C.c_int32), ("idx", C.c_int32), ("n_xform", C.c_int32), ("xform", C.c_int32 * 4), ("xa", C.c_float * 4),
+                ("xb", C.c_float * 4), ("xc", C.c_float * 4), ("p", C.c_float), ("inv_p", C.c_float), ("scale", C.c_float)]
+
+
+class VoronoiRTerm(C.Structure):
+    """sonar_voronoi_rterm"""
+    _fields_ = [("op", C.c_int32), ("idx1", C.c_int32), ("idx2", C.c_int32), ("n_fn", C.c_int32), ("n_ridge", C.c_int32),
+                ("fn", C.c_int32 * 4), ("fa", C.c_float * 4), ("fb", C.c_float * 4), ("ridge", C.c_float * 4), ("eps", C.c_float),
+                ("temperature", C.c_float), ("scale", C.c_float)]
+
+
+class VoronoiProgram(C.Structure):
+    """sonar_voronoi_program"""
+    _fields_ = [("n_d", C.c_int32), ("n_r", C.c_int32), ("d", VoronoiDTerm * 4), ("r", VoronoiRTerm * 4)]
+
+
+def voronoi_program(dterms, rterms) -> VoronoiProgram:
+    """The POD program of one octave from the flattened terms (py/noise_generation.py, ``voronoi_parse_*``).  A distance term is a dict
+    metric, idx, p, scale, xforms [(kind, a, b, c)]; a result term a dict op, idx1, idx2, eps, temperature, scale, fns [(kind, a, b)],
+    ridges [exp, innermost first]."""
+    if not 1 <= len(dterms) <= VORONOI_MAX_TERMS or not 1 <= len(rterms) <= VORONOI_MAX_TERMS:
+        raise NotImplementedError(f"Voronoi: {len(dterms)} distance and {len(rterms)} result terms in one octave (at most {VORONOI_MAX_TERMS} each)")
+    prog = VoronoiProgram()
+    prog.n_d, prog.n_r = len(dterms), len(rterms)
+    for t, term in enumerate(dterms):
+        d = prog.d[t]
+        d.metric, d.idx, d.n_xform = VORONOI_METRICS[term["metric"]], int(term.get("idx", 2)), len(term.get("xforms", ()))
+        p = float(term.get("p", 3.0))
+        d.p, d.inv_p, d.scale = p, (1 / p if p != 0 else math.inf), float(term.get("scale", 1.0))
+        for k, (kind, a, b, c) in enumerate(term.get("xforms", ())):
+            d.xform[k], d.xa[k], d.xb[k], d.xc[k] = VORONOI_XFORMS[kind], float(a), float(b), float(c)
+    for t, term in enumerate(rterms):
+        r = prog.r[t]
+        r.op, r.idx1, r.idx2 = VORONOI_OPS[term["op"]], int(term.get("idx1", 0)), int(term.get("idx2", 1))
+        r.eps, r.temperature, r.scale = float(term.get("eps", 1e-06)), float(term.get("temperature", 50.0)), float(term.get("scale", 1.0))
+        r.n_fn, r.n_ridge = len(term.get("fns", ())), len(term.get("ridges", ()))
+        for k, (kind, a, b) in enumerate(term.get("fns", ())):
+            r.fn[k], r.fa[k], r.fb[k] = VORONOI_XFORMS[kind], float(a), float(b)
+        for k, e in enumerate(term.get("ridges", ())):
+            r.ridge[k] = float(e)
+    return prog
+
+
+class VoronoiFuzz:
+    """The state the three launches of a fuzz distance term share (sonar_voronoi_fuzz_octave_f32): the term's index and ``fuzz``, the
+    ordered-integer statistics on the device and the uniforms -- ``u`` [B, C, H, W, N] (replay) or the stream (seed, stream_id, elem_offset)
+    that ``philox_uniform`` would fill for that shape."""
+
+    def __init__(self, term: int, fuzz: float, rows: int, device, *, u: Optional[torch.Tensor] = None, seed: int = 0, stream_id: int = 0,
+                 elem_offset: int = 0):
+        self.term, self.fuzz, self.u, self.seed, self.stream_id, self.elem_offset = int(term), float(fuzz), u, int(seed), int(stream_id), int(elem_offset)
+        self.stats = torch.zeros(2 + 2 * rows, dtype=torch.int32, device=device)
+        self.stats[0::2] = -1  # 0xFFFFFFFF in the minimum slots, 0 in the maximum slots
+
+
+def voronoi_octave_(out: Optional[torch.Tensor], fp: torch.Tensor, prog: VoronoiProgram, *, scale: float, z_norm: float, amplitude: float = 1.0,
+                    final_div: Optional[float] = None, aux: Optional[torch.Tensor] = None, fuzz: Optional[VoronoiFuzz] = None,
+                    fuzz_pass: int = 2, shape=None) -> Optional[torch.Tensor]:
+    """sonar_voronoi_octave_f32: ``out`` [B][C][H][W] += octave(fp [B][C][N][3]) * amplitude, then / final_div when given; in place.  With
+    ``fuzz`` (sonar_voronoi_fuzz_octave_f32) ``fuzz_pass`` 0 and 1 only reduce into ``fuzz.stats`` (``out`` None, ``shape`` given)."""
+    shape = tuple(out.shape) if out is not None else tuple(shape)
+    if len(shape) != 4 or fp.ndim != 4 or fp.shape[3] != 3 or tuple(fp.shape[:2]) != shape[:2]:
+        raise SonarHipError(f"voronoi_octave_: feature points of shape {tuple(fp.shape)} for an output of shape {shape}")
+    if (out is not None and not out.is_contiguous()) or not fp.is_contiguous():
+        raise SonarHipError("voronoi_octave_: contiguous tensors only")
+    if out is None and (fuzz is None or fuzz_pass == 2):
+        raise SonarHipError("voronoi_octave_: only the reducing fuzz passes run without an output")
+    if aux is not None and aux.numel() < VORONOI_MAX_TERMS:
+        raise SonarHipError(f"voronoi_octave_: aux holds {aux.numel()} values, {VORONOI_MAX_TERMS} are read")
+    b, c, h, w = shape
+    n = int(fp.shape[2])
+    tail = (float(scale), float(z_norm), float(amplitude), 1.0 if final_div is None else float(final_div),
+            0 if final_div is None else VORONOI_FINAL_DIV, C.addressof(prog))
+    if fuzz is None:
+        _check(load().sonar_voronoi_octave_f32(_dev(fp, "fp"), _dev(out, "out"), _opt(aux, "aux"), int(b), int(c), int(h), int(w), n, *tail, _stream()),
+               "sonar_voronoi_octave_f32")
+        return out
+    if fuzz.stats.numel() != 2 + 2 * b * c * h or (fuzz.u is not None and (fuzz.u.numel() != b * c * h * w * n or not fuzz.u.is_contiguous())):
+        raise SonarHipError(f"voronoi_octave_: fuzz statistics of {fuzz.stats.numel()} words or uniforms that do not fit {shape} x {n}")
+    _check(load().sonar_voronoi_fuzz_octave_f32(_dev(fp, "fp"), _opt(out, "out"), _opt(aux, "aux"), _opt(fuzz.u, "u"),
+                                                _dev(fuzz.stats, "stats", torch.int32), int(b), int(c), int(h), int(w), n, *tail, int(fuzz_pass),
+                                                fuzz.term, fuzz.fuzz, fuzz.seed, fuzz.stream_id, fuzz.elem_offset, _stream()),
+           "sonar_voronoi_fuzz_octave_f32")
+    return out
+
+
+def voronoi_gradient_(acc: torch.Tensor, r1: torch.Tensor, r2: torch.Tensor, scale: float) -> torch.Tensor:
+    """sonar_voronoi_gradient_f32: ``acc`` [..., H, W] += gradient_magnitude(r1, r2) * scale (replicate padding); in place."""
+    if acc.ndim < 2 or r1.shape != acc.shape or r2.shape != acc.shape or not (acc.is_contiguous() and r1.is_contiguous() and r2.is_contiguous()):
+        raise SonarHipError(f"voronoi_gradient_: planes of shapes {tuple(r1.shape)}, {tuple(r2.shape)} for {tuple(acc.shape)} (contiguous, equal)")
+    h, w = acc.shape[-2:]
+    _check(load().sonar_voronoi_gradient_f32(_dev(r1, "r1"), _dev(r2, "r2"), _dev(acc, "acc"), acc.numel() // max(h * w, 1), int(h), int(w),
+                                             float(scale), _stream()), "sonar_voronoi_gradient_f32")
+    return acc
+
+
+def voronoi_fuzz_add_(x: torch.Tensor, u: torch.Tensor, fuzz: float) -> torch.Tensor:
+    """sonar_voronoi_fuzz_add_f32: ``x`` += u * (fuzz * 2) - fuzz; in place."""
+    if u.numel() != x.numel() or not (x.is_contiguous() and u.is_contiguous()):
+        raise SonarHipError(f"voronoi_fuzz_add_: {u.numel()} uniforms for {x.numel()} values (contiguous)")
+    _check(load().sonar_voronoi_fuzz_add_f32(_dev(x, "x"), _dev(u, "u"), x.numel(), float(fuzz * 2), float(fuzz), _stream()),
+           "sonar_voronoi_fuzz_add_f32")
+    return x
+
+
+def voronoi_acc_(acc: torch.Tensor, x: torch.Tensor, scale: float, final_div: Optional[float] = None) -> torch.Tensor:
+    """sonar_voronoi_acc_f32: ``acc`` = acc + x * scale, then / final_div when given; in place."""
+    if x.numel() != acc.numel() or not (x.is_contiguous() and acc.is_contiguous()):
+        raise SonarHipError(f"voronoi_acc_: {x.numel()} values into {acc.numel()} (contiguous)")
+    _check(load().sonar_voronoi_acc_f32(_dev(acc, "acc"), _dev(x, "x"), acc.numel(), float(scale), 1.0 if final_div is None else float(final_div),
+                                        0 if final_div is None else VORONOI_FINAL_DIV, _stream()), "sonar_voronoi_acc_f32")
     return acc
 
 

@@ -42,6 +42,7 @@ from .noise_generation import (
     StudentTNoiseGenerator,
     UniformNoiseGenerator,
     VoronoiNoiseGenerator,
+    VoronoiOffPath,
     WaveletFilteredNoiseGenerator,
     WaveletNoiseGenerator,
 )
@@ -482,6 +483,27 @@ class AdvancedCollatzNoise(AdvancedNoiseBase):
         mix_ns = (mix_chain.make_noise_sampler(x, *args, normalized=False, **kwargs)
                   if mix_chain is not None and self.output_mode.startswith("noise_") else None)
         return super().make_noise_sampler(x, *args, normalized=normalized, seed_noise_sampler=seed_ns, mix_noise_sampler=mix_ns, **kwargs)
+
+
+class AdvancedVoronoiNoise(AdvancedNoiseBase):
+    """py/noise.py:446-467: VoronoiNoiseGenerator, its feature points optionally from a chain (sampled un-normalised on a [B, C, N, 3]
+    latent).  The sampler's keyword arguments (``cpu`` among them: replay or generate mode) reach the generator through NoiseSampler."""
+
+    ns_factory_arg_keys = tuple(VoronoiNoiseGenerator.ng_params(no_super=True))
+
+    @property
+    def ns_factory(self):
+        return VoronoiNoiseGenerator
+
+    def clone_key(self, k):
+        if k == "custom_noise" and getattr(self, "custom_noise", None) is not None:
+            return self.custom_noise.clone()
+        return super().clone_key(k)
+
+    def make_noise_sampler(self, x, *args, normalized=True, **kwargs):
+        if x.ndim != 4:
+            raise ValueError("Can only handle 4+ dimensional latents")
+        return super().make_noise_sampler(x, *args, normalized=normalized, noise_sampler_factory=getattr(self, "custom_noise", None), **kwargs)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1538,8 +1560,8 @@ NOISE_SAMPLERS: dict[NoiseType, Callable] = {
     NoiseType.PYRAMID_MIX_BISLERP: _pyramid_mix("pyramid_mix_bislerp", "bislerp", 0.5),
     NoiseType.PYRAMID_MIX_AREA: _pyramid_mix("pyramid_mix_area", "area", 0.5),
     NoiseType.WAVELET: NoiseSampler.wrap(WaveletNoiseGenerator),
-    NoiseType.VORONOI_FUZZ: NoiseSampler.wrap(VoronoiNoiseGenerator),
-    NoiseType.VORONOI_MIX: NoiseSampler.wrap(VoronoiNoiseGenerator),
+    NoiseType.VORONOI_FUZZ: NoiseSampler.wrap(VoronoiOffPath),  # the two types keep refusing; AdvancedVoronoiNoise is the way in
+    NoiseType.VORONOI_MIX: NoiseSampler.wrap(VoronoiOffPath),
 }
 
 

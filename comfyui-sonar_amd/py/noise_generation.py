@@ -850,7 +850,7 @@ def _off_path(type_name: str):
     return _OffPath
 
 
-VoronoiNoiseGenerator = _off_path("voronoi")
+VoronoiOffPath = _off_path("voronoi")  # what the two NoiseType.VORONOI_* entries and the node keep pointing at: the registry is unchanged
 CollatzOffPath = _off_path("collatz")  # what NoiseType.COLLATZ and its node keep pointing at: the registry is unchanged
 ScatternetFilteredNoiseGenerator = _off_path("scatternet_filtered")
 
@@ -950,6 +950,338 @@ class CollatzNoiseGenerator(NoiseGenerator):
         if self.adjust_scale:
             result = utils.normalize_to_scale(result, -1.0, 1.0, dim=tuple(range(1 if result.ndim < 4 else 2, result.ndim)))
         return result
+
+
+class VoronoiNoiseGenerator(NoiseGenerator):
+    """py/noise_generation.py:1291-1904.  An octave is one launch of csrc/voronoi.hip (sonar_voronoi_octave_f32: grid, wrap, distance
+    program, the four smallest distances per pixel and the result program, accumulated into the output; the last octave's launch also
+    divides by the total amplitude), plus one raw pass and one max reduction per ``cellid`` term.  The mode strings are parsed here exactly
+    as voronoi_distance / voronoi_result / voronoi_call_mode split them (``+`` terms of weight 1 / len, ``:k=v`` keyword arguments, one
+    leading ``_`` stripped per call level) and flattened into the kernel's POD program.  The feature points come from ``rand_like``: the
+    host generator in replay mode, one Philox stream per drawn tensor in generate mode (keyed by global batch index under
+    ``shard_offset``), or from ``noise_sampler_factory``.  float32, 4-D latents.  ``cellid`` divides by the largest index of the tensor
+    this call sees: under ``shard_offset`` the shard's, and so do the result ``fuzz``'s extremes.  ``gradient_magnitude`` (replicate padding)
+    and the result ``fuzz`` work on whole planes: as the outermost mode of a ``+`` term, each inner term is a launch into a temporary plane,
+    followed by the stencil kernel, or by the min / max reduction, one drawn tensor of uniforms, the fused add and ``normalize_to_scale``;
+    the octave is then summed term by term in the reference's order.  The ``fuzz`` distance mode (one term per expression, outermost) is
+    three launches of the kernel: two that reduce -- the inner distance over the whole tensor, the fuzzed distance per (b, c, y) row -- and
+    the real pass that rescales; nothing is read on the host and no [B, C, H, W, N] tensor is written (generate mode: the kernel computes
+    the uniforms' stream elements; replay mode: the host's draw is copied over, as every replayed draw is).  Not built
+    (NotImplementedError naming the expression): ``median_distance``, ``softmin:use_sorted``, ``f:idx`` outside 0..3, other ``pad_mode``s, a plane mode under another
+    wrapper, and a plane mode beside a bare ``f`` term (the reference's in-place sums alias the sorted tensor there)."""
+
+    name = "voronoi"
+    MIN_DIMS = 4
+    MAX_DIMS = 4
+
+    voronoi_distance_modes = frozenset(("angle_sigmoid", "angle_tanh", "angle", "chebyshev", "euclidean", "fractal_norm", "fuzz", "manhatten",
+                                        "minkowski", "quadratic", "weight"))
+    voronoi_result_modes = frozenset(("cellid", "diff", "diff2", "f", "f1", "f2", "f3", "f4", "fractal_norm", "fuzz", "inv_f", "inv_f1", "inv_f2",
+                                      "inv_f3", "inv_f4", "gradient_magnitude", "median_distance", "ridge", "softmin"))
+
+    @classmethod
+    def ng_params(cls, *, no_super: bool = False):
+        result = {"n_points": (32,), "distance_mode": ("euclidean",), "z_initial": 0.0, "z_increment": 1.0, "z_max": 100000,
+                  "z_max_mode": "reset", "z_range": None, "result_mode": ("f1",), "octaves": 1, "octave_mode": "same_features",
+                  "lacunarity": 2.0, "gain": 0.5, "initial_amplitude": 1.0, "initial_scale": 1.0, "noise_sampler_factory": None,
+                  "normalized": False}
+        return result if no_super else super().ng_params() | result
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.feature_points = self.grid_xyz = None
+        self.noise_samplers = None
+        self.n_points = tuple(max(2, val) for val in self.n_points)
+        self._programs = {}
+
+    # ---- the mode strings (py/noise_generation.py:1455-1845), flattened instead of evaluated
+    @classmethod
+    def _mode_name(cls, name: str, *, result: bool) -> str:
+        name = name.strip().lower()
+        if name not in (cls.voronoi_result_modes if result else cls.voronoi_distance_modes):
+            raise ValueError(f"Bad Voronoi {'result' if result else 'distance'} mode {name}")
+        return name
+
+    @staticmethod
+    def _strip(kwargs: dict) -> dict:
+        return {k[1:] if k.startswith("_") and len(k) > 1 else k: v for k, v in kwargs.items()}
+
+    @staticmethod
+    def _fractal(kwargs: dict, what: str, default_name: str):
+        name, mode = kwargs.pop("name", default_name), kwargs.pop("mode", "sin")
+        scale, multiplier = kwargs.pop("scale", 0.1), kwargs.pop("multiplier", 10.0)
+        if mode not in ("sin", "cos"):
+            raise ValueError(f"Bad mode parameter for fractal_norm {what} mode, must be one of: sin, cos")
+        return name, (f"fractal_{mode}", float(scale), float(multiplier))
+
+    @classmethod
+    def _parse_distance(cls, name: str, kwargs: dict, xforms: tuple, expr: str, top: bool = False) -> dict:
+        name, kwargs = cls._mode_name(name, result=False), cls._strip(kwargs)
+        if name == "fuzz":
+            if not top:
+                raise NotImplementedError(f"Voronoi distance mode {expr!r}: fuzz is built as the outermost mode of a term only")
+            inner, fuzz = kwargs.pop("name", "euclidean"), float(kwargs.pop("fuzz", 0.25))
+            return cls._parse_distance(inner, kwargs, (), expr) | {"fuzz": fuzz}
+        if name in ("weight", "fractal_norm"):
+            if name == "weight":
+                inner = kwargs.pop("name", "euclidean")
+                step = ("weight", float(kwargs.pop("h", 1.0)), float(kwargs.pop("w", 1.0)), float(kwargs.pop("z", 0.25)))
+            else:
+                inner, fn = cls._fractal(kwargs, "distance", "euclidean")
+                step = (*fn, 0.0)
+            if len(xforms) == hip_lib.VORONOI_MAX_CHAIN:
+                raise NotImplementedError(f"Voronoi distance mode {expr!r}: more than {hip_lib.VORONOI_MAX_CHAIN} nested transforms")
+            return cls._parse_distance(inner, kwargs, (*xforms, step), expr)
+        term = {"metric": name, "xforms": xforms}
+        if name == "minkowski":
+            term["p"] = float(kwargs.get("p", 3.0))
+        if name.startswith("angle"):
+            idx = int(kwargs.get("idx", 2))
+            if not -3 <= idx < 3:
+                raise IndexError(f"index {idx} is out of bounds for dimension 0 with size 3")
+            term["idx"] = idx % 3
+        return term
+
+    @classmethod
+    def _parse_result(cls, name: str, kwargs: dict, fns: tuple, ridges: tuple, expr: str, top: bool = False) -> dict:
+        name, kwargs = cls._mode_name(name, result=True), cls._strip(kwargs)
+        if name == "median_distance":
+            raise NotImplementedError(f"Voronoi result mode {expr!r}: {name} needs the whole sorted row per pixel")
+        if name in ("fuzz", "gradient_magnitude"):
+            if not top:
+                raise NotImplementedError(f"Voronoi result mode {expr!r}: {name} is built as the outermost mode of a term only")
+            if name == "fuzz":
+                inner, fuzz = kwargs.pop("name", "f1"), float(kwargs.pop("fuzz", 0.25))
+                return {"op": "fuzz", "fuzz": fuzz, "inner": (cls._parse_result(inner, kwargs, (), (), expr),)}
+            name1, name2, pad_mode = kwargs.pop("name1", "f4"), kwargs.pop("name2", "f4"), kwargs.pop("pad_mode", "replicate")
+            if pad_mode != "replicate":
+                raise NotImplementedError(f"Voronoi result mode {expr!r}: gradient_magnitude is built with pad_mode=replicate only")
+            first = cls._parse_result(name1, dict(kwargs), (), (), expr)
+            return {"op": "gradient_magnitude", "inner": (first,) if name2 == name1 else (first, cls._parse_result(name2, dict(kwargs), (), (), expr))}
+        if name == "ridge":
+            inner, exp = kwargs.pop("name", "diff"), float(kwargs.pop("exp", -10.0))
+            if len(ridges) == hip_lib.VORONOI_MAX_CHAIN:
+                raise NotImplementedError(f"Voronoi result mode {expr!r}: more than {hip_lib.VORONOI_MAX_CHAIN} nested ridges")
+            return cls._parse_result(inner, kwargs, fns, (exp, *ridges), expr)
+        if name == "fractal_norm":
+            inner, fn = cls._fractal(kwargs, "result", "diff")
+            if len(fns) == hip_lib.VORONOI_MAX_CHAIN:
+                raise NotImplementedError(f"Voronoi result mode {expr!r}: more than {hip_lib.VORONOI_MAX_CHAIN} nested fractal_norms")
+            return cls._parse_result(inner, kwargs, (*fns, fn), ridges, expr)
+        term = {"fns": fns, "ridges": ridges}  # ridges: innermost first
+        if name == "softmin":
+            if kwargs.get("use_sorted") is not None:
+                raise NotImplementedError(f"Voronoi result mode {expr!r}: softmin with use_sorted needs the whole sorted row per pixel")
+            return term | {"op": "softmin", "temperature": float(kwargs.get("temperature", 50.0))}
+        if name == "cellid":
+            return term | {"op": "cellid"}
+        inv = name.startswith("inv_")
+        base = name[4:] if inv else name
+        if inv:
+            eps = kwargs.pop("eps", 1e-06)
+            if isinstance(eps, str):
+                raise TypeError("unsupported operand type(s) for +: 'Tensor' and 'str'")
+            term["eps"] = float(eps)
+        if base in ("diff", "diff2"):
+            idxs = (int(kwargs.get("idx1", 0)), int(kwargs.get("idx2", 1)))
+            term |= {"op": base, "idx1": idxs[0], "idx2": idxs[1]}
+        else:
+            if base != "f" and "idx" in kwargs:
+                raise TypeError("_voronoi_result_f() got multiple values for keyword argument 'idx'")
+            idxs = (int(kwargs.get("idx", 0)) if base == "f" else int(base[1:]) - 1,)
+            term |= {"op": "inv_f" if inv else "f", "idx1": idxs[0], "idx2": idxs[0]}
+        if not all(0 <= i <= 3 for i in idxs):
+            raise NotImplementedError(f"Voronoi result mode {expr!r}: idx outside 0..3 needs the whole sorted row per pixel")
+        return term
+
+    @staticmethod
+    def _split_terms(expr: str, scale_key: str):
+        """voronoi_distance / voronoi_result's own split: [(name, kwargs, scale)]."""
+        modes = expr.split("+")
+        base = 1.0 / len(modes)
+        for mode in modes:
+            if ":" in mode:
+                name, *rest = mode.split(":")
+                kwargs = dict(tuple(val.strip() for val in di.split("=", 1)) for di in rest)
+                yield name, kwargs, base * float(kwargs.pop(scale_key, 1.0))
+            else:
+                yield mode, {}, base
+
+    @classmethod
+    def parse_modes(cls, distance_mode: str, result_mode: str):
+        """(distance terms, result terms) of one octave, as hip_lib.voronoi_program takes them."""
+        dterms = [cls._parse_distance(name, kwargs, (), distance_mode, top=True) | {"scale": scale}
+                  for name, kwargs, scale in cls._split_terms(distance_mode, "dscale")]
+        if sum("fuzz" in d for d in dterms) > 1:
+            raise NotImplementedError(f"Voronoi distance mode {distance_mode!r}: at most one fuzz term per octave expression")
+        rterms = [cls._parse_result(name, kwargs, (), (), result_mode, top=True) | {"scale": scale}
+                  for name, kwargs, scale in cls._split_terms(result_mode, "rscale")]
+        if len(rterms) > 1 and any(cls._is_plane(r) for r in rterms) and any(
+                cls._is_view(r) or (r["op"] == "fuzz" and cls._is_view(r["inner"][0])) for r in rterms):
+            raise NotImplementedError(f"Voronoi result mode {result_mode!r}: a plane mode (fuzz, gradient_magnitude) beside a bare f term -- the "
+                                      "reference's in-place sums write through the sorted distances there")
+        return dterms, rterms
+
+    @staticmethod
+    def _is_plane(term: dict) -> bool:
+        return term["op"] in ("fuzz", "gradient_magnitude")
+
+    @staticmethod
+    def _is_view(term: dict) -> bool:
+        """A bare f term: the reference returns a view of the sorted distances."""
+        return term["op"] == "f" and not term["fns"] and not term["ridges"]
+
+    def get_distance_mode(self, octave: int) -> str:
+        return self.distance_mode[octave % len(self.distance_mode)]
+
+    def get_result_mode(self, octave: int) -> str:
+        return self.result_mode[octave % len(self.result_mode)]
+
+    def _program(self, octave: int):
+        """(distance terms, result terms) of the octave; refuses before anything is drawn or launched."""
+        key = (self.get_distance_mode(octave), self.get_result_mode(octave))
+        if key not in self._programs:
+            dterms, rterms = self.parse_modes(*key)
+            leaves = [leaf for r in rterms for leaf in (r["inner"] if self._is_plane(r) else (r,))]
+            for group in ([r for r in rterms if not self._is_plane(r)], *([leaf] for leaf in leaves)):
+                if group:
+                    hip_lib.voronoi_program(dterms, group)  # the term counts
+            self._programs[key] = (dterms, rterms, max((max(r.get("idx1", 0), r.get("idx2", 0)) for r in leaves), default=0))
+        dterms, rterms, top = self._programs[key]
+        sets = self.octaves if self.octave_mode == "new_features" else 1
+        n = self.n_points[(octave % sets) % len(self.n_points)]  # the feature set this octave reads
+        if top >= n:
+            raise IndexError(f"index {top} is out of bounds for dimension 5 with size {n}")
+        return dterms, rterms
+
+    # ---- state (py/noise_generation.py:1362-1447)
+    def voronoi_reset(self, *args):
+        self.z_curr = self.z_initial
+        octave_range = tuple(range(self.octaves if self.octave_mode == "new_features" else 1))
+        shapes = [(self.batch, self.channels, self.n_points[octave % len(self.n_points)], 3) for octave in octave_range]
+        if self.noise_sampler_factory is not None and self.noise_samplers is None:
+            self.noise_samplers = tuple(
+                self.noise_sampler_factory.make_noise_sampler(torch.zeros(shape, device=self.device, dtype=self.dtype), cpu=self.cpu, normalized=False)
+                for shape in shapes)
+        points = []
+        for octave, shape in zip(octave_range, shapes):
+            if self.noise_samplers is None:
+                pts = self.rand_like(fun=torch.rand, shape=shape)
+            else:
+                pts = self.noise_samplers[octave](*args)
+                utils.pop_stats(pts)
+                pts = utils.normalize_to_scale(pts, target_min=0.0, target_max=1.0, dim=(-1, -2))
+            utils.pop_stats(pts)
+            points.append(utils.as_f32(pts.to(self.device)).contiguous())
+        self.feature_points = tuple(points)
+        if self.grid_xyz is None:
+            self.grid_xyz = (self.height, self.width)  # the grid itself is computed from the indices inside the kernel
+
+    def get_feature_points(self, octave: int) -> Tensor:
+        result = self.feature_points[octave % len(self.feature_points)]
+        odd_octave = (octave % 2) == 1
+        om = self.octave_mode
+        if (om == "same_invert_odd" and odd_octave) or (om == "same_invert_even" and not odd_octave):
+            return 1.0 - result
+        if octave > 0 and om in {"same_roll_chan_up", "same_roll_chan_down"}:
+            return torch.roll(result, (-1 if om == "same_roll_chan_up" else 1) * (octave % 3), dims=(1,))
+        if octave > 0 and om in {"same_roll_dir_up", "same_roll_dir_down"}:
+            return torch.roll(result, (-1 if om == "same_roll_dir_up" else 1) * (octave % 3), dims=(3,))
+        return result
+
+    def generate(self, *args):
+        programs = [self._program(octave) for octave in range(self.octaves)]
+        if self.grid_xyz is None or self.feature_points is None or self.z_max == 0:
+            self.voronoi_reset(*args)
+        elif self.z_max != 0 and abs(self.z_initial - self.z_curr) > abs(self.z_max):
+            if self.z_max_mode == "reset":
+                self.voronoi_reset(*args)
+            elif self.z_max_mode == "bounce":
+                self.z_increment = -self.z_increment
+                self.z_curr += self.z_increment
+            else:
+                self.curr_z = self.z_initial  # (the reference's own slip: z_curr keeps running)
+        z_range = fallback(self.z_range, max(self.height, self.width))
+        z_norm = (self.z_curr % z_range) / z_range
+        self.z_curr += self.z_increment
+        shape = tuple(self.shape)
+        result = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        amplitude, scale, total_amplitude = self.initial_amplitude, self.initial_scale, 0.0
+        for octave in range(self.octaves):
+            dterms, rterms = programs[octave]
+            fp = self.get_feature_points(octave).contiguous()
+            total_amplitude += abs(amplitude)
+            final_div = (total_amplitude if total_amplitude != 0 else 1.0) if octave == self.octaves - 1 else None
+            fuzz = self._fuzz_passes(fp, dterms, scale, z_norm)
+            if not any(self._is_plane(r) for r in rterms):
+                self._launch(result, fp, dterms, rterms, scale, z_norm, amplitude, final_div, fuzz=fuzz)
+            else:
+                hip_lib.voronoi_acc_(result, self._plane_octave(fp, dterms, rterms, scale, z_norm, fuzz), amplitude, final_div)
+            amplitude *= self.gain
+            scale *= self.lacunarity
+        return result
+
+    def _fuzz_passes(self, fp: Tensor, dterms, scale: float, z_norm: float):
+        """The octave's fuzz distance term, if any: one draw (the host's tensor in replay mode; in generate mode only a stream id is taken
+        and the kernel computes the element it needs), then the two reducing launches -- the inner distance's whole-tensor extremes and
+        the fuzzed distance's extremes per (b, c, y) row -- into device statistics every later launch of the octave reads."""
+        term = next((t for t, d in enumerate(dterms) if "fuzz" in d), None)
+        if term is None:
+            return None
+        shape = tuple(self.shape)
+        n = int(fp.shape[2])
+        rows = shape[0] * shape[1] * shape[2]
+        if self.cpu:
+            u = utils.as_f32(self.rand_like(fun=torch.rand, shape=(*shape, n))).contiguous()
+            fuzz = hip_lib.VoronoiFuzz(term, dterms[term]["fuzz"], rows, self.device, u=u)
+        else:
+            seed, stream = self.device_key()
+            fuzz = hip_lib.VoronoiFuzz(term, dterms[term]["fuzz"], rows, self.device, seed=seed, stream_id=stream,
+                                       elem_offset=self.latent_elem_offset(math.prod(shape[1:]) * n))
+        prog = hip_lib.voronoi_program(dterms, [{"op": "f"}])
+        for fuzz_pass in (0, 1):
+            hip_lib.voronoi_octave_(None, fp, prog, scale=scale, z_norm=z_norm, fuzz=fuzz, fuzz_pass=fuzz_pass, shape=shape)
+        return fuzz
+
+    def _launch(self, out: Tensor, fp: Tensor, dterms, rterms, scale: float, z_norm: float, amplitude: float = 1.0, final_div=None, *,
+                fuzz=None) -> Tensor:
+        """out += (the terms' sum) * amplitude: one launch, after a raw pass and a max reduction per cellid term."""
+        aux = None
+        for t, r in enumerate(rterms):
+            if r["op"] == "cellid":  # cellids.max() of the whole tensor, on the device: the raw indices of a first pass, reduced
+                aux = torch.ones(hip_lib.VORONOI_MAX_TERMS, dtype=torch.float32, device=self.device) if aux is None else aux
+                raw = hip_lib.voronoi_program(dterms, [{"op": "cellid_raw", "fns": r["fns"]}])
+                ids = hip_lib.voronoi_octave_(torch.zeros_like(out), fp, raw, scale=scale, z_norm=z_norm, amplitude=1.0, fuzz=fuzz)
+                aux[t:t + 1].copy_(hip_lib.minmax_rows(ids, 1, ids.numel())[1])
+        return hip_lib.voronoi_octave_(out, fp, hip_lib.voronoi_program(dterms, rterms), scale=scale, z_norm=z_norm, amplitude=amplitude, aux=aux,
+                                       final_div=final_div, fuzz=fuzz)
+
+    def _plane_octave(self, fp: Tensor, dterms, rterms, scale: float, z_norm: float, fuzz=None) -> Tensor:
+        """An octave with plane modes, summed term by term in the reference's order: the leading pointwise terms in one launch (their sum
+        starts the octave), every later term on its own."""
+        octv = torch.zeros(tuple(self.shape), dtype=torch.float32, device=self.device)
+        lead = 0
+        while not self._is_plane(rterms[lead]):
+            lead += 1
+        if lead:
+            self._launch(octv, fp, dterms, rterms[:lead], scale, z_norm, fuzz=fuzz)
+        for r in rterms[lead:]:
+            if not self._is_plane(r):
+                self._launch(octv, fp, dterms, [r], scale, z_norm, fuzz=fuzz)
+                continue
+            planes = [self._launch(torch.zeros_like(octv), fp, dterms, [leaf | {"scale": 1.0}], scale, z_norm, fuzz=fuzz) for leaf in r["inner"]]
+            if r["op"] == "gradient_magnitude":
+                hip_lib.voronoi_gradient_(octv, planes[0], planes[-1], r["scale"])
+                continue
+            inner = planes[0]
+            lo, hi = hip_lib.minmax_rows(inner, 1, inner.numel())
+            rmin, rmax = float(lo), float(hi)  # (the reference reads both on the host too: they are normalize_to_scale's targets)
+            spread = max(abs(rmin), abs(rmax)) * r["fuzz"]
+            u = self.rand_like(fun=torch.rand, shape=tuple(self.shape))
+            utils.pop_stats(u)
+            hip_lib.voronoi_fuzz_add_(inner, utils.as_f32(u).contiguous(), spread)
+            hip_lib.voronoi_acc_(octv, utils.normalize_to_scale(inner, rmin, rmax, dim=(-2, -1)).contiguous(), r["scale"])
+        return octv
 
 
 def _lowrank_mvn(loc, cov_factor, cov_diag):

@@ -466,6 +466,104 @@ int sonar_collatz_chain_f32(const float* seeds, const float* seed_ext, float* ou
 int sonar_collatz_mix_f32(float* acc, const float* out1, const float* second, int second_mode, int64_t outer, int64_t len, int64_t inner,
                           int64_t chain_length, float scale, void* stream);
 
+/* ---------------------------------------------------------------- VoronoiNoiseGenerator */
+/* One octave of VoronoiNoiseGenerator.generate_octave (py/noise_generation.py:1847-1869) as one launch, accumulated into the output:
+ * out[b][c][y][x] = out + result * amplitude, and with SONAR_VORONOI_FINAL_DIV the sum is then divided by final_div (the generator's
+ * total amplitude).  fp [B][C][N][3] are the plane's feature points in [0, 1]; the grid (y / H, x / W, z_norm), the two `(v * scale) % 1`
+ * and the toroidal difference d = (g - f + 0.5) % 1 - 0.5 are the reference's own fp32 operations, one rounding each, `%` as
+ * torch.remainder.  One thread per pixel, a workgroup inside one (b, c) plane, the plane's points staged through LDS
+ * SONAR_VORONOI_CHUNK at a time; per pixel one pass over the points keeps the four smallest distances and the index of the smallest
+ * (and the online-softmax sums of `softmin`) in registers.
+ * The program is the parsed distance_mode / result_mode of the octave (the host flattens the strings):
+ *   distance = sum over n_d terms of metric(xform_k(... xform_1(d))) * scale; a transform is WEIGHT (d * (a, b, c)) or FRACTAL_SIN /
+ *              FRACTAL_COS (d + a * fun(d * b)); the metrics are the reference's (MANHATTEN is its euclidean), ANGLE* read component idx
+ *              of F.normalize(d) (eps 1e-12).
+ *   result   = sum over n_r terms of ridge_k(... ridge_1(op(e))) * scale with e = fn_k(... fn_1(distance)), fn = a * fun(distance * b)
+ *              (the result fractal_norm: the selection runs on e), ridge = 1 - a * v.  Ops: F (the idx1-th smallest), INV_F
+ *              (1 / (F + eps)), DIFF (F[idx2] - F[idx1]), DIFF2 ((v2 - v1) / (v2 + v1 + 1e-6)), SOFTMIN (sum e * softmax(-|d| * temperature)),
+ *              CELLID (index of the smallest / aux[term] + 1, aux a device array of SONAR_VORONOI_MAX_TERMS floats: the whole tensor's
+ *              largest index, reduced from a CELLID_RAW pass) and CELLID_RAW (the index of the smallest as a float).
+ * SONAR_ERR_ARG: a NULL pointer (aux only with a CELLID term), out == fp, a negative size, a size of 2^31 or more, N < 2 (with pixels to
+ * compute), a term count outside 1..SONAR_VORONOI_MAX_TERMS, a chain longer than SONAR_VORONOI_MAX_CHAIN, an unknown metric, transform, op
+ * or flag, idx outside its range.  SONAR_ERR_UNSUPPORTED: N > SONAR_VORONOI_MAX_POINTS.  All checked before anything touches the HIP
+ * runtime; an empty output launches nothing. */
+#define SONAR_VORONOI_MAX_TERMS 4
+#define SONAR_VORONOI_MAX_CHAIN 4
+#define SONAR_VORONOI_MAX_POINTS 4096
+#define SONAR_VORONOI_CHUNK 256
+#define SONAR_VORONOI_FINAL_DIV 1
+#define SONAR_VORONOI_D_EUCLIDEAN 0
+#define SONAR_VORONOI_D_MANHATTEN 1
+#define SONAR_VORONOI_D_CHEBYSHEV 2
+#define SONAR_VORONOI_D_MINKOWSKI 3
+#define SONAR_VORONOI_D_QUADRATIC 4
+#define SONAR_VORONOI_D_ANGLE 5
+#define SONAR_VORONOI_D_ANGLE_TANH 6
+#define SONAR_VORONOI_D_ANGLE_SIGMOID 7
+#define SONAR_VORONOI_X_WEIGHT 0
+#define SONAR_VORONOI_X_FRACTAL_SIN 1
+#define SONAR_VORONOI_X_FRACTAL_COS 2
+#define SONAR_VORONOI_R_F 0
+#define SONAR_VORONOI_R_INV_F 1
+#define SONAR_VORONOI_R_DIFF 2
+#define SONAR_VORONOI_R_DIFF2 3
+#define SONAR_VORONOI_R_SOFTMIN 4
+#define SONAR_VORONOI_R_CELLID 5
+#define SONAR_VORONOI_R_CELLID_RAW 6
+typedef struct sonar_voronoi_dterm {
+    int32_t metric, idx, n_xform;
+    int32_t xform[SONAR_VORONOI_MAX_CHAIN];
+    float xa[SONAR_VORONOI_MAX_CHAIN], xb[SONAR_VORONOI_MAX_CHAIN], xc[SONAR_VORONOI_MAX_CHAIN];
+    float p, inv_p /* minkowski: p and 1 / p, the latter formed in double */, scale;
+} sonar_voronoi_dterm;
+typedef struct sonar_voronoi_rterm {
+    int32_t op, idx1, idx2, n_fn, n_ridge;
+    int32_t fn[SONAR_VORONOI_MAX_CHAIN] /* SONAR_VORONOI_X_FRACTAL_SIN / _COS */;
+    float fa[SONAR_VORONOI_MAX_CHAIN], fb[SONAR_VORONOI_MAX_CHAIN];
+    float ridge[SONAR_VORONOI_MAX_CHAIN] /* innermost first */;
+    float eps, temperature, scale;
+} sonar_voronoi_rterm;
+typedef struct sonar_voronoi_program {
+    int32_t n_d, n_r;
+    sonar_voronoi_dterm d[SONAR_VORONOI_MAX_TERMS];
+    sonar_voronoi_rterm r[SONAR_VORONOI_MAX_TERMS];
+} sonar_voronoi_program;
+int sonar_voronoi_octave_f32(const float* fp, float* out, const float* aux, int64_t B, int64_t C, int64_t H, int64_t W, int64_t N,
+                             float scale, float z_norm, float amplitude, float final_div, int flags, const sonar_voronoi_program* prog,
+                             void* stream);
+
+/* The fuzz distance mode (py/noise_generation.py:1586-1603) as three launches of the octave kernel; distance term `fuzz_term` of the
+ * program is the fuzzed one, its chain and metric the inner mode.  `stats` is a device array of 2 + 2 B C H words holding floats as
+ * unsigned integers of the same order (a negative float's bits inverted, a positive one's sign bit set): [0] / [1] the minimum / maximum
+ * of the inner distance over the whole tensor, [2 + 2 r] / [3 + 2 r] those of the fuzzed distance over (W, N) of row r = (b C + c) H + y;
+ * the caller fills the minimum slots with 0xFFFFFFFF and the maximum slots with 0 before pass 0.
+ *   pass 0  reduces the inner distance into stats[0..1] (rmin, rmax = result.aminmax()); writes nothing else, out may be NULL
+ *   pass 1  reduces inner + (u * 2 f - f), f = max(|rmin|, |rmax|) * fuzz formed in double from the device values, into the row slots
+ *           (normalize_to_scale(dim=(-2, -1)) on [B, C, H, W, N] groups over (W, N)); out may be NULL
+ *   pass 2  the real pass: the fuzzed distance rescaled with sonar_minmax_rescale_f32's device function between its row's extremes to
+ *           [rmin, rmax] (eps 1e-7), then the term's scale, the other terms, the selection and the result as in sonar_voronoi_octave_f32
+ * No value is read on the host and no [B, C, H, W, N] tensor is written.  The uniforms: `u` [B][C][H][W][N] when given (replay mode),
+ * else the element elem_offset + flat index of the stream (seed, stream_id) that sonar_philox_uniform_f32 fills -- the same values
+ * hip_lib.philox_uniform gives for that shape, so all three passes see one draw.
+ * SONAR_ERR_ARG beyond sonar_voronoi_octave_f32's: NULL stats, stats or u equal to another buffer, pass outside 0..2, fuzz_term outside
+ * the program's distance terms, fuzz NaN, elem_offset or stream_id outside [0, 2^48). */
+int sonar_voronoi_fuzz_octave_f32(const float* fp, float* out, const float* aux, const float* u, uint32_t* stats, int64_t B, int64_t C,
+                                  int64_t H, int64_t W, int64_t N, float scale, float z_norm, float amplitude, float final_div, int flags,
+                                  const sonar_voronoi_program* prog, int pass, int fuzz_term, double fuzz, uint64_t seed, uint64_t stream_id,
+                                  int64_t elem_offset, void* stream);
+
+/* The result modes that work on whole planes of inner results (each inner term one sonar_voronoi_octave_f32 launch into a temporary):
+ *  sonar_voronoi_gradient_f32  gradient_magnitude with replicate padding (clamped indices): acc[p][y][x] += sqrt(dx^2 + dy^2) * scale,
+ *                              dx = r1[y][x + 1] - r2[y][x - 1], dy = r1[y + 1][x] - r2[y - 1][x]; r2 may be r1.
+ *  sonar_voronoi_fuzz_add_f32  the result fuzz's x += u * twice_fuzz - fuzz, each step rounded (the rescale around it is the existing
+ *                              min / max reduction and sonar_minmax_rescale_f32).
+ *  sonar_voronoi_acc_f32       acc = acc + x * scale, then / final_div with SONAR_VORONOI_FINAL_DIV.
+ * SONAR_ERR_ARG: a NULL pointer, an output equal to an input, a negative size, 2^31 values or more, an unknown flag; a size of 0 launches
+ * nothing. */
+int sonar_voronoi_gradient_f32(const float* r1, const float* r2, float* acc, int64_t planes, int64_t H, int64_t W, float scale, void* stream);
+int sonar_voronoi_fuzz_add_f32(float* x, const float* u, int64_t n, float twice_fuzz, float fuzz, void* stream);
+int sonar_voronoi_acc_f32(float* acc, const float* x, int64_t n, float scale, float final_div, int flags, void* stream);
+
 /* A pending global normalisation of a noise tensor (py/utils.py:100-105): the decision scale_noise(normalized=True) would take,
  * computed ON THE DEVICE from the tensor's (sum, sumsq) partials and left in device memory, so that the kernel that consumes the
  * noise (the sampler-step kernels below take it as `noise_norm`, nullable) applies `((v - mean) / std) * factor` -- only the parts
