@@ -201,6 +201,8 @@ SIGNATURES = {
     "sonar_group_scale_noise_f32": (_I, [_P, _I, _I, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _F, _P]),
     "sonar_shuffle_gather_f32": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _I, _P, _I, _P]),
     "sonar_shuffle_generate_f32": (_I, [_P, _P, _I, _I64, _I64, _I64, _I64, _I64, _I, _F, _I, _U64, _U64, _I64, _P]),
+    "sonar_pattern_break_route": (_I, [_I64]),
+    "sonar_pattern_break_f32": (_I, [_P, _P, _I64, _F, _F, _I, _I, _I, _P, _I64, _P, _P]),
     "sonar_collatz_chain_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _D, _D, _D, _D, _D, _D, _I, _I, _I, _P]),
     "sonar_collatz_mix_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _I64, _I64, _F, _P]),
     "sonar_voronoi_octave_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _F, _F, _I, _P, _P]),
@@ -2089,6 +2091,31 @@ def voronoi_acc_(acc: torch.Tensor, x: torch.Tensor, scale: float, final_div: Op
     _check(load().sonar_voronoi_acc_f32(_dev(acc, "acc"), _dev(x, "x"), acc.numel(), float(scale), 1.0 if final_div is None else float(final_div),
                                         0 if final_div is None else VORONOI_FINAL_DIV, _stream()), "sonar_voronoi_acc_f32")
     return acc
+
+
+# ------------------------------------------------------------------------------------------------ pattern-break (csrc/pattern_break.hip)
+PATTERN_BREAK_WS = 2048                                    # SONAR_PATTERN_BREAK_WS: floats of (lo, hi) partials between the launches
+PATTERN_BREAK_ROUTES = {None: 0, "one": 1, "three": 2}     # SONAR_PATTERN_BREAK_AUTO / _ONE / _THREE
+
+
+def pattern_break(x: torch.Tensor, detail_scale: float, percentage: float, blend_mode: str, restore_scale: bool, *, route: Optional[str] = None,
+                  out: Optional[torch.Tensor] = None, want_stats: bool = True):
+    """sonar_pattern_break_f32 on a contiguous fp32 tensor: (a new tensor unless ``out`` is given, the (sum, sumsq) partials of it or
+    None).  ``detail_scale`` is 1 + detail_level / 10.  ``route`` None takes one launch up to SONAR_PATTERN_BREAK_ONE_LAUNCH_MAX values and
+    three beyond; "one" / "three" force either -- the same bits.  Nothing is read back on the host."""
+    if blend_mode not in BLEND_IDS:
+        raise SonarHipError(f"pattern_break: unknown blend mode {blend_mode!r}")
+    if route not in PATTERN_BREAK_ROUTES:
+        raise SonarHipError(f"pattern_break: route {route!r}; None, 'one' or 'three'")
+    out = torch.empty_like(x) if out is None else out
+    if out.shape != x.shape:
+        raise SonarHipError(f"pattern_break: shape mismatch {tuple(out.shape)} vs {tuple(x.shape)}")
+    ws = torch.empty(PATTERN_BREAK_WS, dtype=torch.float32, device=x.device)
+    partials = new_partials(x.device) if want_stats else None
+    _check(load().sonar_pattern_break_f32(_dev(x, "x"), _dev(out, "out"), x.numel(), float(detail_scale), float(percentage), BLEND_IDS[blend_mode],
+                                          int(bool(restore_scale)), PATTERN_BREAK_ROUTES[route], _dev(ws, "ws"), ws.numel(),
+                                          _opt(partials, "partials", torch.float64), _stream()), "sonar_pattern_break_f32")
+    return out, partials
 
 
 IMAGE_BLEND_IDS = BLEND_IDS | {"simple_add": 3}  # SONAR_IMAGE_BLEND_ADD

@@ -832,6 +832,35 @@ class ShuffledNoise(CustomNoiseItemBase):
         return noise_sampler
 
 
+class PatternBreakNoise(CustomNoiseItemBase):
+    """py/noise.py:2016-2077: a chain's un-normalised noise through ``utils.pattern_break``, then scaled.  The filter's apply launch leaves the
+    statistics of its output with the tensor, so ``scale_noise(normalized=True)`` runs no statistics sweep.  ``percentage == 0`` hands back
+    the inner chain's own sampler (with ``normalized`` passed through), as the reference does."""
+
+    def __init__(self, factor, *, noise, detail_level: float, percentage: float, restore_scale: bool, blend_mode: str = "lerp", blend_function=None):
+        super().__init__(factor, noise=noise, detail_level=detail_level, percentage=percentage, restore_scale=restore_scale,
+                         blend_function=blend_function or utils.BLENDING_MODES[blend_mode])
+
+    def clone_key(self, k):
+        if k == "noise":
+            return self.noise.clone()
+        return super().clone_key(k)
+
+    def make_noise_sampler(self, x, sigma_min, sigma_max, *args, normalized=True, **kwargs):
+        factor = self.factor
+        ns = self.noise.make_noise_sampler(x, *args, sigma_min=sigma_min, sigma_max=sigma_max,
+                                           normalized=normalized if self.percentage == 0 else False, **kwargs)
+        if self.percentage == 0:
+            return ns
+        noise_filter = partial(utils.pattern_break, percentage=self.percentage, detail_level=self.detail_level,
+                               blend_function=self.blend_function, restore_scale=self.restore_scale)
+
+        def noise_sampler(sigma, sigma_next):
+            return scale_noise(noise_filter(ns(sigma, sigma_next)), factor, normalized=normalized)
+
+        return noise_sampler
+
+
 class RNGStates:
     """py/utils.py:736-791: a snapshot of Python's ``random``, torch's CPU generator and the current device's default generator, which
     can be put back (``set_states``) and taken again (``update``).  The device generator is captured as (seed, Philox offset): generate

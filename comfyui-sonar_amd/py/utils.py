@@ -257,6 +257,38 @@ def elementwise_shuffle_by_dim(t: Tensor, *, dim: int = -1, prob: float = 1.0, n
     return out if t.dtype == torch.float32 else out.to(t.dtype)
 
 
+def pattern_break(noise: Tensor, *, percentage: float = 0.5, detail_level: float = 0.0, restore_scale: bool = True,
+                  blend_function: Optional[Callable] = None, route: Optional[str] = None) -> Tensor:
+    """py/utils.py:575-596 (after Extraltodeus' noise_latent_perlinpinpin): the tensor rescaled to [-1, 1] between its own extremes, every
+    value sent through ``erfinv(2 (|v| 1e6 mod 11) / 11 - 1)``, optionally rescaled to the input's extremes, and blended with the input.
+    One to three fused launches (csrc/pattern_break.hip) with no read-back on the host; a new tensor, which carries the (sum, sumsq)
+    statistics of its values for the ``scale_noise`` that follows.
+
+    ``blend_function`` is one of ``BLENDING_MODES``' values (``lerp`` by default, where the reference has ``torch.lerp``): the blend runs
+    inside the kernel, so any other callable raises ``NotImplementedError``.  float16 / bfloat16 and non-contiguous inputs are computed in
+    float32 and cast back (the reference's ``lerp`` raises on the mixed dtypes).  A float32 result keeps its statistics tag also when it is
+    copied into a non-contiguous input's layout; a result rounded to another dtype carries none.  ``route`` (None, "one", "three") forces the one-launch or
+    the three-launch route; the bits are the same."""
+    from . import noise_generation
+
+    mode = "lerp" if blend_function is None else next((k for k, f in BLENDING_MODES.items() if f is blend_function), None)
+    if mode is None:
+        raise NotImplementedError("pattern_break: a Python blend_function would run on the host; only BLENDING_MODES' functions run here")
+    _require_device(noise, "pattern_break")
+    if noise.numel() == 0:
+        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0. Specify the reduction dim with the 'dim' argument.")
+    if noise_generation.current_batch_offset() != 0:
+        raise NotImplementedError("pattern_break: this filter reduces across the samples of the batch, which a sharded batch "
+                                  "splits (reduce on one rank, or use a per-sample dim)")
+    x = as_f32(noise)
+    out, partials = hip_lib.pattern_break(x, 1 + detail_level / 10, percentage, mode, restore_scale, route=route)
+    if noise.dtype != torch.float32:
+        return out.to(noise.dtype)
+    if not noise.is_contiguous():  # as_f32 made a contiguous copy: hand the result back in the input's layout (the sums know no order)
+        out = torch.empty_like(noise).copy_(out)
+    return attach_stats(out, partials)
+
+
 def tensor_to(tensor: Tensor, dest) -> Tensor:
     """py/utils.py:112-121."""
     device = dest.device if isinstance(dest, Tensor) else dest

@@ -564,6 +564,32 @@ int sonar_voronoi_gradient_f32(const float* r1, const float* r2, float* acc, int
 int sonar_voronoi_fuzz_add_f32(float* x, const float* u, int64_t n, float twice_fuzz, float fuzz, void* stream);
 int sonar_voronoi_acc_f32(float* acc, const float* x, int64_t n, float scale, float final_div, int flags, void* stream);
 
+/* ---------------------------------------------------------------- PatternBreakNoise */
+/* utils.pattern_break (py/utils.py:575-596) on a contiguous fp32 tensor of n values, out != x:
+ *   v = clamp(((x - lo) / ((hi - lo) + 1e-7)) * 2 - 1, -1, 1)           lo, hi = min, max of x (a NaN never wins)
+ *   a = 2 * (fmod(|v| * 1e6, 11) / 11) - 1                              every step one fp32 rounding, fmod exact
+ *   result = clamp(((detail_scale * erfinv(a)) * sqrt(2)) * 0.2, -1, 1) erfinv(-1) = -inf reaches the clamp; NaN stays NaN
+ *   restore_scale: result = clamp(((result - rlo) / ((rhi - rlo) + 1e-7)) * (hi - lo) + lo, lo, hi), rlo, rhi = min, max of result,
+ *                  hi - lo formed in double and rounded once (the reference takes them through .item())
+ *   out = blend(blend_mode, x, result, percentage)                      SONAR_BLEND_*
+ * detail_scale is 1 + detail_level / 10, formed in double by the caller.  Nothing is read on the host.  `route` SONAR_PATTERN_BREAK_THREE:
+ * three launches (extremes of x; extremes of the result, only with restore_scale; apply) through (lo, hi) partials in `ws`;
+ * SONAR_PATTERN_BREAK_ONE: one workgroup runs the three phases in one launch; SONAR_PATTERN_BREAK_AUTO: ONE up to
+ * SONAR_PATTERN_BREAK_ONE_LAUNCH_MAX values (sonar_pattern_break_route(n) tells which).  Both routes give the same bits in `out`.
+ * ws: SONAR_PATTERN_BREAK_WS floats (ws_floats says how many there are).  stats (nullable): SONAR_NPART (sum, sumsq) pairs of `out`, as
+ * sonar_stats_f32 writes them (the summation order depends on the route).
+ * SONAR_ERR_ARG: x, out or ws NULL, a pointer not aligned to its element, out == x, ws == x or out, n <= 0, an unknown blend mode or route,
+ * ws_floats < SONAR_PATTERN_BREAK_WS.  All checked before anything touches the HIP runtime. */
+#define SONAR_PATTERN_BREAK_NPART 512
+#define SONAR_PATTERN_BREAK_WS (4 * SONAR_PATTERN_BREAK_NPART)
+#define SONAR_PATTERN_BREAK_ONE_LAUNCH_MAX 4096
+#define SONAR_PATTERN_BREAK_AUTO 0
+#define SONAR_PATTERN_BREAK_ONE 1
+#define SONAR_PATTERN_BREAK_THREE 2
+int sonar_pattern_break_route(int64_t n);
+int sonar_pattern_break_f32(const float* x, float* out, int64_t n, float detail_scale, float percentage, int blend_mode, int restore_scale,
+                            int route, float* ws, int64_t ws_floats, double* stats, void* stream);
+
 /* A pending global normalisation of a noise tensor (py/utils.py:100-105): the decision scale_noise(normalized=True) would take,
  * computed ON THE DEVICE from the tensor's (sum, sumsq) partials and left in device memory, so that the kernel that consumes the
  * noise (the sampler-step kernels below take it as `noise_norm`, nullable) applies `((v - mean) / std) * factor` -- only the parts
