@@ -226,6 +226,7 @@ SIGNATURES = {
     "sonar_dtcwt_c2q_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
     "sonar_dtcwt_q2c_f64": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
     "sonar_dtcwt_c2q_f64": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "sonar_scat_layer_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _I, _P, _I, _F, _I64, _I64, _P]),
     "sonar_philox_normal_chain_f32": (_I, [_P, _P, _I64, _U64, _U64, _I64, _P]),
     "sonar_perlin_generate_chain_f32": (_I, [_P, _P, _P, _I64, _I64, _F, _U64, _U64, _I64, _P]),
     "sonar_pyramid_generate_acc_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _I, _U64, _U64, _I64, _P]),
@@ -1740,6 +1741,42 @@ def dtcwt_c2q(bands: torch.Tensor):
     fn = load().sonar_dtcwt_c2q_f32 if kind == "f32" else load().sonar_dtcwt_c2q_f64
     _check(fn(_dev(bands, "bands", bands.dtype), *[_dev(o, "plane", bands.dtype) for o in outs], B * Cc, h, w, _stream()), f"sonar_dtcwt_c2q_{kind}")
     return tuple(outs)
+
+
+# ------------------------------------------------------------------------------------------------ scattering layer (csrc/scatternet.hip)
+SCAT_TILE_H, SCAT_TILE_W = 16, 32  # SONAR_SCAT_TILE_H / _W: output values per workgroup tile
+_SCAT_TAPS: dict = {}
+
+
+def scat_layer(x: torch.Tensor, *, biort: str = "near_sym_a", magbias: float = 1e-2, channels: Optional[tuple] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sonar_scat_layer_f32: one scattering layer of a contiguous fp32 [B, C, H, W] tensor -> [B, 7 C, ceil(H / 2), ceil(W / 2)], band-major
+    (channel band * C + c; band 0 the pooled low-pass, 1..6 the smoothed magnitudes at 15 .. 165 degrees).  ``channels=(k0, nk)`` computes
+    and writes only the channels k0 .. k0 + nk - 1, into a [B, nk, ...] tensor; their values are those of the full call.  The taps are
+    ``py.dtcwt.biort_filters(biort)``'s (its NotImplementedError for a bank that is not built in)."""
+    taps = _SCAT_TAPS.get(biort)
+    if taps is None:
+        from .py.dtcwt import biort_filters
+
+        h0o, _g0o, h1o, _g1o = biort_filters(biort)
+        taps = _SCAT_TAPS[biort] = ((C.c_float * len(h0o))(*[float(v) for v in h0o]), (C.c_float * len(h1o))(*[float(v) for v in h1o]))
+    if not isinstance(x, torch.Tensor) or x.ndim != 4:
+        raise SonarHipError("scat_layer: expected a [B, C, H, W] tensor")
+    B, Cc, H, W = x.shape
+    if min(Cc, H, W) < 1:
+        raise SonarHipError(f"scat_layer: empty plane in {tuple(x.shape)}")
+    k0, nk = (0, 7 * Cc) if channels is None else (int(channels[0]), int(channels[1]))
+    if k0 < 0 or nk < 1 or k0 + nk > 7 * Cc:
+        raise SonarHipError(f"scat_layer: channel window [{k0}, {k0 + nk}) outside the {7 * Cc} output channels")
+    shape = (B, nk, (H + 1) // 2, (W + 1) // 2)
+    xp = _dev(x, "x")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise SonarHipError(f"scat_layer: out has shape {tuple(out.shape)}, expected {shape}")
+    _check(load().sonar_scat_layer_f32(xp, _dev(out, "out"), B, Cc, H, W, taps[0], len(taps[0]), taps[1], len(taps[1]), float(magbias), k0, nk,
+                                       _stream()), "sonar_scat_layer_f32")
+    return out
 
 
 def minmax_rescale(x: torch.Tensor, rows: int, inner: int, lo: torch.Tensor, hi: torch.Tensor, eps: float, target_min: float,

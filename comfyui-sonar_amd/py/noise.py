@@ -39,6 +39,7 @@ from .noise_generation import (
     PowerOldNoiseGenerator,
     PyramidNoiseGenerator,
     PyramidOldNoiseGenerator,
+    ScatternetFilteredNoiseGenerator,
     StudentTNoiseGenerator,
     UniformNoiseGenerator,
     VoronoiNoiseGenerator,
@@ -1525,6 +1526,53 @@ class WaveletFilteredNoise(CustomNoiseItemBase):
         gen = WaveletFilteredNoiseGenerator(x, *args, sigma_min=sigma_min, sigma_max=sigma_max, normalized=False, noise_sampler=ns_low,
                                             noise_sampler_high=ns_high, **blends, **(kwargs | opts))
         return lambda sigma, sigma_next: scale_noise(gen(sigma, sigma_next), factor, normalized=normalize)
+
+
+class ScatternetFilteredNoise(CustomNoiseItemBase):
+    """py/noise.py:1596-1662: a chain's noise (``noise=None``: Gaussian, drawn by the generator) through ScatternetFilteredNoiseGenerator,
+    then scaled.  In the ``_adjusted`` modes the inner chain is built for the plane enlarged by ``2**|scatternet_order|``, so that the
+    kept window fills the latent; the ``_scaled`` modes upscale instead.  Reached through the Python API: there is no node yet.  What is
+    built, reproduced and refused: the generator's docstring."""
+
+    def __init__(self, factor, *, noise=None, padding_mode: str = "symmetric", use_symmetric_filter: bool = False, magbias: float = 1e-2,
+                 output_offset: float = 0.0, output_mode: str = "channels_adjusted", scatternet_order: int = 1,
+                 per_channel_scatternet: bool = False, normalize_noise: bool = False, normalize=None, **kwargs):
+        super().__init__(factor, noise=noise, padding_mode=padding_mode, use_symmetric_filter=use_symmetric_filter, magbias=magbias,
+                         output_offset=output_offset, output_mode=output_mode, scatternet_order=scatternet_order,
+                         per_channel_scatternet=per_channel_scatternet, normalize_noise=normalize_noise, normalize=normalize, **kwargs)
+
+    def clone_key(self, k):
+        if k == "noise" and self.noise is not None:
+            return self.noise.clone()
+        return super().clone_key(k)
+
+    def make_noise_sampler(self, x, sigma_min, sigma_max, *args, normalized=True, **kwargs):
+        if x.ndim != 4:
+            raise ValueError("Currently can only handle 4 dimensional latents")
+        return _for_latent_dtype(x, lambda x32: self._sampler(x32, sigma_min, sigma_max, *args, normalized=normalized, **kwargs))
+
+    def _sampler(self, x, sigma_min, sigma_max, *args, normalized=True, **kwargs):
+        factor = self.factor
+        normalize = self.get_normalize("normalize", normalized)
+        opts = kwargs | getattr(self, "ns_kwargs", {})
+        params = dict(mode=self.padding_mode, use_symmetric_filter=self.use_symmetric_filter, magbias=self.magbias,
+                      output_offset=self.output_offset, output_mode=self.output_mode, scatternet_order=self.scatternet_order,
+                      per_channel_scatternet=self.per_channel_scatternet) | opts
+        # every refusal before the inner chain is built or anything touches the device
+        ScatternetFilteredNoiseGenerator._refusals(ScatternetFilteredNoiseGenerator.ng_params() | params)
+        internal_ns = None
+        if self.noise is not None:
+            grow = 2 ** abs(self.scatternet_order) if self.output_mode.endswith("_adjusted") and self.scatternet_order != 0 else 1
+            ref_x = x if grow == 1 else x.new_zeros(*x.shape[:-2], x.shape[-2] * grow, x.shape[-1] * grow)
+            internal_ns = self.noise.make_noise_sampler(ref_x, *args, sigma_min=sigma_min, sigma_max=sigma_max,
+                                                        normalized=self.normalize_noise, **kwargs)
+        ns = ScatternetFilteredNoiseGenerator(x, *args, sigma_min=sigma_min, sigma_max=sigma_max, normalized=False, noise_sampler=internal_ns,
+                                              **params)
+
+        def noise_sampler(sigma, sigma_next):
+            return scale_noise(ns(sigma, sigma_next), factor, normalized=normalize)
+
+        return noise_sampler
 
 
 # --------------------------------------------------------------------------------------------------

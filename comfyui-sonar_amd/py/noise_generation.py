@@ -852,7 +852,144 @@ def _off_path(type_name: str):
 
 VoronoiOffPath = _off_path("voronoi")  # what the two NoiseType.VORONOI_* entries and the node keep pointing at: the registry is unchanged
 CollatzOffPath = _off_path("collatz")  # what NoiseType.COLLATZ and its node keep pointing at: the registry is unchanged
-ScatternetFilteredNoiseGenerator = _off_path("scatternet_filtered")
+
+
+def scatternet_window(*, out_size: int, initial_size: int, increment: int, output_offset: float) -> int:
+    """py/noise_generation.py:2166-2178: where the kept window starts in the scattered tensor's dim 2 (``out_size`` long; channels, or
+    elements in the flat modes).  Offsets of magnitude below 1 are fractions of the room ``(out_size - initial_size) / increment``, rounded
+    half to even by Python's ``round``; others are truncated to steps of ``increment``; negative ones count from the end."""
+    offset_size = (out_size - initial_size) / increment
+    if output_offset == 0 or abs(output_offset) >= 1:
+        output_offset = int(output_offset)
+        if output_offset < 0:
+            output_offset = (offset_size + 1) + output_offset
+    else:
+        if output_offset < 0:
+            output_offset += 1.0
+        output_offset = round(offset_size * output_offset)
+    return int(output_offset * increment)
+
+
+class ScatternetFilteredNoiseGenerator(FramesToChannelsNoiseGenerator):
+    """py/noise_generation.py:2035-2193: a chain's noise (Gaussian without one) through ``|scatternet_order|`` scattering layers, of which
+    a window of channels (or, in the ``flat`` modes, of elements) is kept and raw-reshaped to the latent.  A layer is one launch of
+    csrc/scatternet.hip; the window is worked out BEFORE the last layer runs, which computes and writes only the channels that cover it
+    (``C`` of ``7 C`` in the default mode).  pytorch_wavelets is absent here and in the reference tree: **parity unpinned**; the layer is
+    pinned to an fp64 statement kept with the tests, built on the transform's own, and to its defining properties.
+
+    Reproduced as the reference has it: ``magbias`` is accepted and never reaches the layer, which runs with ScatLayer's own 1e-2
+    (``scatkwargs``, :2056-2059); ``round`` is Python's (half to even); the result is a raw ``reshape`` of the window.  Refused at
+    construction: ``scatternet_order == 2`` (ScatLayerj2, a two-scale network over q-shift filters with 49 C outputs, is not restated;
+    ``-2`` is the stack of two first-order layers and is built), a ``mode`` other than ``symmetric``, ``use_symmetric_filter`` and any
+    ``biort`` outside the built-in three (``biort_filters``' error).  One deliberate difference: without a noise sampler the Gaussian is
+    drawn at the size the window needs -- enlarged by ``2**|order|`` in the ``_adjusted`` modes, the plane the item builds an inner
+    chain for -- where the reference draws it enlarged in the plain modes only (:2113) and then fails in its final ``reshape`` in both.  A
+    window that does not fit, or does not fill the latent, raises before the last layer is launched."""
+
+    name = "scatternetfilter"
+    MIN_DIMS = 4
+    MAX_DIMS = 4
+    OUTPUT_MODES = ("channels", "channels_adjusted", "channels_scaled", "flat", "flat_adjusted", "flat_scaled")
+    LAYER_MAGBIAS = 1e-2  # ScatLayer's default: the reference never hands its own `magbias` on
+
+    def __init__(self, *args, **kwargs):
+        self._refusals(self.ng_params() | kwargs)
+        super().__init__(*args, **kwargs)
+
+    @staticmethod
+    def _refusals(p: dict) -> None:
+        from .dtcwt import biort_filters
+
+        if p["output_mode"] not in ScatternetFilteredNoiseGenerator.OUTPUT_MODES:
+            raise ValueError("Bad output mode")
+        if p["mode"] != "symmetric":
+            raise NotImplementedError("Scatternet: symmetric extension only (pytorch_wavelets' default)")
+        biort_filters("near_sym_b_bp" if p["use_symmetric_filter"] else p["biort"])
+        if p["scatternet_order"] == 2:
+            raise NotImplementedError("Scatternet: scatternet_order 2 is pytorch_wavelets' ScatLayerj2, a two-scale network over q-shift filters "
+                                      "with 49 C outputs, which is not restated here; -2 is the stack of two first-order layers and is built")
+
+    @classmethod
+    def ng_params(cls):
+        return super().ng_params() | {
+            "mode": "symmetric", "magbias": 1e-02, "use_symmetric_filter": False, "biort": "near_sym_a", "qshift": "qshift_a",
+            "output_offset": 0.0, "scatternet_order": 1, "per_channel_scatternet": False, "output_mode": "channels_adjusted",
+            "upscale_mode": None, "noise_sampler": None,
+        }
+
+    def plan(self, in_shape) -> dict:
+        """Host arithmetic of :2156-2193 for a scattered input of ``in_shape`` [B, C, H, W]: the channel range the last layer computes,
+        the element slice inside it (flat modes) and the shapes on the way; raises where the reference's slice and reshape cannot fill
+        the latent."""
+        adjusted = self.output_mode.endswith(("_scaled", "_adjusted"))
+        output_mode = self.output_mode.split("_", 1)[0] if adjusted else self.output_mode
+        order = abs(self.scatternet_order)
+        per_channel = bool(self.per_channel_scatternet)
+        b, c, h, w = (int(v) for v in in_shape)
+        for _ in range(order):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        base_channels = 1 if per_channel else c
+        k_total = 7**order * base_channels  # channels of the scattered tensor's dim 2
+        if output_mode == "flat":
+            out_size = k_total * h * w
+            initial_size = math.prod(self.shape[(2 if per_channel else 1):])
+        else:
+            out_size = k_total
+            initial_size = base_channels if adjusted else base_channels * ((2**order) ** 2)
+        increment = 1 if output_mode == "flat" else base_channels
+        base_idx = scatternet_window(out_size=out_size, initial_size=initial_size, increment=increment, output_offset=self.output_offset)
+        if base_idx < 0 or initial_size < 1 or base_idx + initial_size > out_size:
+            raise ValueError(f"Scatternet: the window [{base_idx}, {base_idx + initial_size}) runs outside the scattered output of size {out_size} "
+                             f"(output_mode {self.output_mode!r}, output_offset {self.output_offset})")
+        if output_mode == "flat":
+            k0 = base_idx // (h * w)
+            nk = (base_idx + initial_size - 1) // (h * w) - k0 + 1
+            lo = base_idx - k0 * h * w
+            kept = initial_size
+        else:
+            k0, nk, lo = base_idx, initial_size, None
+            kept = nk * min(h, self.height) * min(w, self.width) if output_mode == "channels" else nk * h * w
+        groups = c if per_channel else 1
+        want = math.prod(self.get_adjusted_shape())
+        if b * groups * kept != want:
+            raise ValueError(f"Scatternet: the window holds {b * groups * kept} values, the latent {tuple(self.get_adjusted_shape())} needs {want} "
+                             f"(input {tuple(in_shape)}, output_mode {self.output_mode!r}, scatternet_order {self.scatternet_order})")
+        return {"output_mode": output_mode, "k0": k0, "nk": nk, "lo": lo, "initial_size": initial_size, "h": h, "w": w, "order": order}
+
+    def generate(self, *args):
+        adjusted_shape = self.get_adjusted_shape()
+        scaled = self.output_mode.endswith("_scaled")
+        order = abs(self.scatternet_order)
+        compensation = 2**order
+        if self.noise_sampler is None:
+            grow = compensation if self.output_mode.endswith("_adjusted") and order != 0 else 1  # see the class docstring
+            noise = self.rand_like(shape=(*adjusted_shape[:2], adjusted_shape[-2] * grow, adjusted_shape[-1] * grow))
+        else:
+            noise = self.noise_sampler(*args)
+        utils.pop_stats(noise)
+        if scaled:  # :2127-2140 -- there is no probselect here, so None is bilinear
+            noise = utils.scale_samples(noise, adjusted_shape[-1] * compensation, adjusted_shape[-2] * compensation,
+                                        mode=fallback(self.upscale_mode, "bilinear"))
+        if self.scatternet_order == 0:
+            return self.fix_output_frames(noise)
+        if noise.ndim != 4:
+            raise ValueError(f"Scatternet: the noise to filter must be [B, C, H, W], got {tuple(noise.shape)}")
+        noise = utils.as_f32(noise.to(self.device))
+        batch = noise.shape[0]
+        if noise.shape[1] != self.channels:
+            raise ValueError(f"Scatternet: noise with {noise.shape[1]} channels for a latent with {self.channels}")
+        plan = self.plan(noise.shape)  # before any launch
+        if self.per_channel_scatternet:  # the same kernel on [B * C, 1, H, W]: plane (b, c) is the reference's noise[:, c : c + 1] of sample b
+            noise = noise.reshape(batch * self.channels, 1, *noise.shape[-2:])
+        for _ in range(order - 1):
+            noise = hip_lib.scat_layer(noise, biort=self.biort, magbias=self.LAYER_MAGBIAS)
+        noise = hip_lib.scat_layer(noise, biort=self.biort, magbias=self.LAYER_MAGBIAS, channels=(plan["k0"], plan["nk"]))
+        # [B, nk, h, w], or [B * C, nk, h, w] == the reference's stack / squeeze / movedim result [B, C, (nk,) h, w] as it lies
+        if plan["output_mode"] == "flat":
+            noise = noise.reshape(noise.shape[0], -1)[:, plan["lo"]:plan["lo"] + plan["initial_size"]]
+        elif plan["output_mode"] == "channels":
+            noise = noise[..., :self.height, :self.width]
+        return noise.reshape(adjusted_shape).contiguous()
 
 
 class CollatzNoiseGenerator(NoiseGenerator):

@@ -1054,6 +1054,26 @@ int sonar_dtcwt_q2c_f32(const float* lh, const float* hh, const float* hl, float
 int sonar_dtcwt_c2q_f32(const float* bands, float* lh, float* hh, float* hl, int64_t planes, int64_t h, int64_t w, void* stream);
 int sonar_dtcwt_q2c_f64(const double* lh, const double* hh, const double* hl, double* bands, int64_t planes, int64_t h, int64_t w, void* stream);
 int sonar_dtcwt_c2q_f64(const double* bands, double* lh, double* hh, double* hl, int64_t planes, int64_t h, int64_t w, void* stream);
+/* ---------------------------------------------------------------- ScatternetFilteredNoise
+ * One layer of the dual-tree scattering network (pytorch_wavelets' ScatLayer; py/noise_generation.py:2035-2193), fused
+ * (csrc/scatternet.hip).  x [B][C][H][W] fp32, any H, W >= 1: an odd side is extended by repeating its last row / column (He, We: the
+ * even sizes).  Level-1 DTCWT analysis with the biorthogonal pair h0 (n0 taps) / h1 (n1 taps) under half-sample symmetric extension
+ * (the full modular fold: the halo may be longer than the plane), then
+ *   band 0      the 2 x 2 mean of the low-pass plane
+ *   bands 1..6  s / (sqrt(s + b^2) + b) = sqrt(re^2 + im^2 + b^2) - b of the orientations 15, 45, 75, 105, 135, 165 degrees, s = re^2 + im^2,
+ *               b = magbias, (re, im) the quad combinations of sonar_dtcwt_q2c
+ * band-major: channel k = band * C + c of the [B][7 C][He / 2][We / 2] result.  Only the channels k0 .. k0 + nk - 1 are computed and
+ * written, into out [B][nk][He / 2][We / 2]; a band outside the window is neither filtered nor stored; k0 need not be a multiple of C.
+ * The values of a channel do not depend on the window.  h0 / h1 are HOST arrays (read before the call returns): the lengths 5 / 7
+ * (near_sym_a), 5 / 3 (legall) and 9 / 7 (antonini) are built, anything else is SONAR_ERR_UNSUPPORTED.  One launch: a workgroup per tile of
+ * SONAR_SCAT_TILE_H x SONAR_SCAT_TILE_W output values, band group ({0}, {1, 6}, {2, 5}, {3, 4}) and plane.
+ * SONAR_ERR_ARG: a NULL or misaligned pointer, out == x, C, H or W < 1, B < 0, magbias negative or not finite, a tap not finite, a window
+ * outside [0, 7 C).  SONAR_ERR_UNSUPPORTED: a side beyond SONAR_SCAT_MAX_SIDE, 2^31 workgroups or more.  All checked before the launch. */
+#define SONAR_SCAT_TILE_H 16
+#define SONAR_SCAT_TILE_W 32
+#define SONAR_SCAT_MAX_SIDE 1048576
+int sonar_scat_layer_f32(const float* x, float* out, int64_t B, int64_t C, int64_t H, int64_t W, const float* h0, int n0, const float* h1,
+                         int n1, float magbias, int64_t k0, int64_t nk, void* stream);
 /* normalize_to_scale_adv (py/utils.py:473-510; NormalizeToScaleNoise's advanced mode, py/noise.py:1262-1286): per row of `inner` elements the
  * negative values are rescaled between their own extremes to [min_neg, max_neg] (max_neg >= 0: the row's largest negative value) and the
  * positive ones to [min_pos, max_pos] (min_pos < 0: the row's smallest positive value); zeros stay, a sign whose range is degenerate
