@@ -243,6 +243,9 @@ SIGNATURES = {
     "sonar_wcfg_fused_f32": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _PD, _PD, _I, _I, _PD, _PD, _I, _I, _PD, _PD, _I, _D, _I, _I, _P, _I64, _P]),
     "sonar_wcfg_fused_f64": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I, _PD, _PD, _I, _I, _PD, _PD, _I, _I, _PD, _PD, _I, _D, _I, _I, _P, _I64, _P]),
     "sonar_cast_f32_f64": (_I, [_P, _P, _I64, _P]),
+    "sonar_freeu_hidden_mean_groups": (_I64, [_I64, _I64, _I64]),
+    "sonar_freeu_hidden_mean": (_I, [_I, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "sonar_freeu_apply": (_I, [_I, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I, _P, _P, _P, _P, _D, _I, _F, _P]),
     "sonar_plan_fn_id": (_I, [C.c_char_p]),
     "sonar_plan_fn_nargs": (_I, [_I]),
     "sonar_plan_create": (_P, [_I]),
@@ -331,7 +334,9 @@ def tag_forget(t: torch.Tensor) -> None:
                 TAGGED.pop(key, None)
 
 
-def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> int:
+def _dev(t: torch.Tensor, name: str, dtype=torch.float32, contiguous: bool = True) -> int:
+    """Device address of ``t`` after the checks every kernel argument gets.  ``contiguous=False``: a caller that hands the strides to its
+    kernel itself (the FreeU entry points, after ``freeu_layout``)."""
     global _last_device
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a tensor")
@@ -344,7 +349,7 @@ def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> int:
         raise SonarHipError(f"{name}: tensor lives on {t.device}; the Sonar HIP path only runs on a ROCm device")
     if t.dtype != dtype:
         raise SonarHipError(f"{name}: expected {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise SonarHipError(f"{name}: tensor must be contiguous")
     _last_device = t.device.index
     rec = _recorder  # (one read, as in load())
@@ -2279,6 +2284,71 @@ def signed_rescale(x: torch.Tensor, rows: int, inner: int, min_neg: float, max_n
     return out
 
 
+FREEU_PLAIN, FREEU_FUSED, FREEU_FILTERED = 0, 1, 2  # SONAR_FREEU_*
+
+
+def freeu_layout(x: torch.Tensor, what: str = "freeu"):
+    """(stride_b, stride_c) in elements of a feature map the FreeU kernels address in place, or None when its H x W planes are not
+    contiguous (channels-last, a column slice).  Refuses what the kernels do not take: anything but a 4-D fp32 / fp16 / bf16 device tensor."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise SonarHipError(f"{what}: expected a feature map [B, C, H, W]")
+    if x.dtype == torch.float64:
+        raise NotImplementedError(f"{what}: float64 feature maps are not built in (float32 / float16 / bfloat16)")
+    if x.dtype not in DTYPE_IDS:
+        raise SonarHipError(f"{what}: float32 / float16 / bfloat16 only (got {x.dtype})")
+    if not x.is_cuda:
+        raise SonarHipError(f"{what}: tensor lives on {x.device}; the Sonar HIP path only runs on a ROCm device")
+    B, Cn, H, W = x.shape
+    hw = H * W
+    if (W > 1 and x.stride(3) != 1) or (H > 1 and x.stride(2) != W):
+        return None
+    sb = x.stride(0) if B > 1 else Cn * max(x.stride(1), hw)
+    sc = x.stride(1) if Cn > 1 else hw
+    if sb < hw or sc < hw:  # expanded (stride 0) or overlapping planes: not in place
+        return None
+    return sb, sc
+
+
+def freeu_hidden_mean(x: torch.Tensor):
+    """``(mean, extremes)`` of ``sonar_freeu_hidden_mean``: the fp32 channel mean [B, H*W] over ALL channels of ``x`` and each sample's
+    (min, max) of it [B, 2] -- what ``freeu_apply_`` turns into FreeUExtremeConfig.get_scale's map on the fly.  Nothing is read back."""
+    lay = freeu_layout(x, "freeu_hidden_mean")
+    if lay is None:
+        raise SonarHipError("freeu_hidden_mean: every H x W plane must be contiguous")
+    B, Cn, H, W = x.shape
+    mean = torch.empty((B, H * W), dtype=torch.float32, device=x.device)
+    ext = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+    if x.numel():
+        groups = int(load().sonar_freeu_hidden_mean_groups(B, Cn, H * W))  # few positions, many channels: the channels over several workgroups
+        ws = torch.empty((groups, B, H * W), dtype=torch.float32, device=x.device) if groups > 1 else None
+        _check(load().sonar_freeu_hidden_mean(DTYPE_IDS[x.dtype], _dev(x, "x", x.dtype, contiguous=False), B, Cn, H * W, lay[0], lay[1], _dev(mean, "mean"),
+                                              _dev(ext, "extremes"), _opt(ws, "ws"), 0 if ws is None else ws.numel(), _stream()), "sonar_freeu_hidden_mean")
+    return mean, ext
+
+
+def freeu_apply_(x: torch.Tensor, c0: int, cn: int, *, mode: int, filt: Optional[torch.Tensor] = None, filtered: Optional[torch.Tensor] = None,
+                 hidden=None, scale: float = 1.0, blend_mode: Optional[str] = None, blend: float = 1.0) -> torch.Tensor:
+    """``sonar_freeu_apply`` on channels ``c0 .. c0 + cn - 1`` of ``x``, in place through its strides.  ``mode``: FREEU_PLAIN, FREEU_FUSED
+    (``filt`` [H, W/2+1]: both transforms in LDS, planes of kind 1 / 2) or FREEU_FILTERED (``filtered``: fp32 [B, cn, H, W]).  ``hidden``: the
+    pair ``freeu_hidden_mean`` returned, or None for the scalar ``scale``.  ``blend_mode`` None: the scaled value itself."""
+    lay = freeu_layout(x, "freeu_apply_")
+    if lay is None:
+        raise SonarHipError("freeu_apply_: every H x W plane must be contiguous")
+    B, Cn, H, W = x.shape
+    if blend_mode is not None and blend_mode not in BLEND_IDS:
+        raise SonarHipError(f"freeu_apply_: unknown blend mode {blend_mode!r}")
+    if mode == FREEU_FUSED and (filt is None or filt.numel() != H * (W // 2 + 1)):
+        raise SonarHipError("freeu_apply_: filter size mismatch")
+    if mode == FREEU_FILTERED and (filtered is None or filtered.numel() != B * cn * H * W):
+        raise SonarHipError("freeu_apply_: the filtered temporary does not hold the slice")
+    mean, ext = hidden if hidden is not None else (None, None)
+    _check(load().sonar_freeu_apply(DTYPE_IDS[x.dtype], _dev(x, "x", x.dtype, contiguous=False), B, Cn, H, W, lay[0], lay[1], int(c0), int(cn), int(mode),
+                                    _opt(filt if mode == FREEU_FUSED else None, "filter"), _opt(filtered if mode == FREEU_FILTERED else None, "filtered"),
+                                    _opt(mean, "mean"), _opt(ext, "extremes"), float(scale),
+                                    CFG_BLEND_NONE if blend_mode is None else BLEND_IDS[blend_mode], float(blend), _stream()), "sonar_freeu_apply")
+    return x
+
+
 def max_to_host(x: torch.Tensor) -> float:
     """``x.max().item()`` for a non-empty fp32 device tensor (NaN if any element is NaN) in one launch and one stream wait."""
     x = x.contiguous()
@@ -2365,7 +2435,7 @@ PYRAMID_AHEAD = os.environ.get("SONAR_PYRAMID_AHEAD", "1") != "0"  # plans run a
 PERLIN_AHEAD = os.environ.get("SONAR_PERLIN_AHEAD", "1") != "0"  # plans fuse a normalised Perlin call's three launches (_PerlinAheadHook)
 NOT_RUN = object()      # Plan.run: the step was not issued (a guard changed, an entry point refused): take the ordinary path
 _M64 = 2**64 - 1
-_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_power_any_plan", "sonar_dwt_out_len",
+_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_power_any_plan", "sonar_dwt_out_len", "sonar_freeu_hidden_mean_groups",
                            "sonar_dwt2_ws_bytes", "sonar_wcfg_lowpass_lds_bytes", "sonar_wcfg_fused_ws_bytes", "sonar_pyramid_levels", "sonar_pyramid_route",
                            "sonar_plan_fn_id", "sonar_plan_fn_nargs"))
 PATCH_SLOT, PATCH_STREAM, PATCH_SEED, PATCH_BLOB, PATCH_LEVELS = range(5)

@@ -1140,6 +1140,41 @@ int sonar_wcfg_output_f32(const float* x, const void* result, int result_is_f64,
 /* fp32 -> fp64 conversion of a contiguous buffer (get_context cast, py/wavelet_cfg.py:707,764-765) */
 int sonar_cast_f32_f64(const float* in, double* out, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------- FreeU Extreme (csrc/freeu.hip) */
+/* FreeUExtremeConfig.apply (py/nodes/freeu_extreme.py:187-230) on a UNet feature map x [B][C][H][W] of `dtype` (SONAR_DTYPE_*), addressed
+ * in place: stride_b / stride_c are the batch and channel strides in ELEMENTS, every H x W plane is contiguous.  Arithmetic is fp32, the
+ * result is rounded once (to nearest even) -- the reference rounds a half tensor after every operation.
+ *  sonar_freeu_hidden_mean  get_scale's statistics, two launches, nothing read on the host:
+ *                             mean[b][p] = (sum over ALL C channels of x[b][c][p]) / C       (fp32 [B][HW], HW = H * W; lanes walk p)
+ *                             extremes[b] = (min, max) of mean[b][:]                           (fp32 [B][2]; a NaN makes both NaN, as torch.min / max)
+ *                           ws (fp32, ws_elems values, nullable): with room for G >= 2 copies of mean, G = at most
+ *                           sonar_freeu_hidden_mean_groups(B, C, HW) (host arithmetic: few positions and many channels), the channels are split
+ *                           over G workgroups per 64 positions; their partial sums meet, in order, in the second launch.
+ *  sonar_freeu_apply        the channels c0 .. c0 + cn - 1 of every sample, written in place:
+ *                             f = x                                                  SONAR_FREEU_PLAIN (no power filter)
+ *                             f = irfft2(rfft2(x, ortho) * filter, ortho)            SONAR_FREEU_FUSED: one workgroup per plane, both transforms in
+ *                                                                                    LDS; filter is real [H][W/2+1]; planes of
+ *                                                                                    sonar_power_plane_kind 1 and 2 only (else SONAR_ERR_UNSUPPORTED)
+ *                             f = filtered[(b * cn + c - c0) * HW + p]                SONAR_FREEU_FILTERED: fp32 [B][cn][H][W], made by the caller
+ *                                                                                    (the direct DFT passes for odd / oversized planes)
+ *                             s = mean ? 1 + (scale - 1) * ((mean[b][p] - min_b) / (max_b - min_b)) : scale     (0 / 0 is NaN, not guarded;
+ *                                                                                    scale - 1 formed in double, rounded to fp32 once)
+ *                             v = f * s;  x = blend_mode == SONAR_CFG_BLEND_NONE ? v : blend(x, v, blend)       (SONAR_BLEND_*, as sonar_blend_f32)
+ *                           FUSED transforms the whole plane before any of it is stored and reads the original value again (presumably an L2 hit: the
+ *                           workgroup loaded the plane microseconds earlier; not measured) instead of keeping a second copy in LDS.  The hidden-mean launch
+ *                           must precede this one on the same stream (it reads every channel, the slice's included).
+ * SONAR_ERR_ARG: unknown dtype / mode / blend mode, a negative size, a channel window outside [0, C), a stride smaller than the plane, a
+ * required pointer NULL or misaligned for its element type, mean without extremes. */
+#define SONAR_FREEU_PLAIN 0
+#define SONAR_FREEU_FUSED 1
+#define SONAR_FREEU_FILTERED 2
+int64_t sonar_freeu_hidden_mean_groups(int64_t B, int64_t C, int64_t HW);
+int sonar_freeu_hidden_mean(int dtype, const void* x, int64_t B, int64_t C, int64_t HW, int64_t stride_b, int64_t stride_c, float* mean,
+                            float* extremes, float* ws, int64_t ws_elems, void* stream);
+int sonar_freeu_apply(int dtype, void* x, int64_t B, int64_t C, int64_t H, int64_t W, int64_t stride_b, int64_t stride_c, int64_t c0,
+                      int64_t cn, int mode, const float* filter, const float* filtered, const float* mean, const float* extremes, double scale,
+                      int blend_mode, float blend, void* stream);
+
 /* ---------------------------------------------------------------- prepared call plans (host floor of rows C, G1, P, Y, PW) */
 /* The reference composes a sampler step from Python closures (py/noise.py:137-257, py/noise_generation.py:134-258); at the batch sizes
  * a ComfyUI run uses (1-4, cfg3's 64) the interpreter work per step outweighs the kernels.  A plan is the step resolved once: the entry
