@@ -15,7 +15,7 @@ namespace sonar {
 // ---- analysis along W: x[rows][W] -> tmp[rows][2][w]
 template <typename T>
 __global__ void __launch_bounds__(kBlock) dwt_rows_kernel(const T* __restrict__ x, T* __restrict__ tmp, int64_t rows, int W,
-                                                           int w, Taps<T> tp, int mode) {
+                                                           int w, LongTaps<T> tp, int mode) {
     kernarg_touch_for(x, tmp, rows, W, w, tp, mode);
     const int64_t total = rows * w;
     const int F = tp.len;
@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(kBlock) dwt_rows_kernel(const T* __restrict__ 
 // ---- analysis along H: tmp[planes][H][2][w] -> ll[planes][h][w], hi[planes][3][h][w]
 template <typename T>
 __global__ void __launch_bounds__(kBlock) dwt_cols_kernel(const T* __restrict__ tmp, T* __restrict__ ll, T* __restrict__ hi,
-                                                           int64_t planes, int H, int h, int w, Taps<T> tp, int mode) {
+                                                           int64_t planes, int H, int h, int w, LongTaps<T> tp, int mode) {
     kernarg_touch_for(tmp, ll, hi, planes, H, h, w, tp, mode);
     const int64_t total = planes * h * w;
     const int F = tp.len;
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(kBlock) dwt_cols_kernel(const T* __restrict__ 
 template <typename T>
 __global__ void __launch_bounds__(kBlock) idwt_cols_kernel(const T* __restrict__ ll, int ll_h, int ll_w,
                                                             const T* __restrict__ hi, T* __restrict__ tmp, int64_t planes, int h,
-                                                            int w, int Hr, Taps<T> tp, int mode) {
+                                                            int w, int Hr, LongTaps<T> tp, int mode) {
     kernarg_touch_for(ll, ll_h, ll_w, hi, tmp, planes, h, w, Hr, tp, mode);
     const int64_t total = planes * Hr * w;
     const int64_t hw = (int64_t)h * w;
@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(kBlock) idwt_cols_kernel(const T* __restrict__
 // ---- synthesis along W: tmp[planes][2][Hr][w] -> out[planes][Ho][Wo] (cropped)
 template <typename T>
 __global__ void __launch_bounds__(kBlock) idwt_rows_kernel(const T* __restrict__ tmp, T* __restrict__ out, int64_t planes, int w,
-                                                            int Hr, int Ho, int Wo, Taps<T> tp, int mode) {
+                                                            int Hr, int Ho, int Wo, LongTaps<T> tp, int mode) {
     kernarg_touch_for(tmp, out, planes, w, Hr, Ho, Wo, tp, mode);
     const int64_t total = planes * Ho * Wo;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(kBlock) wcfg_output_kernel(const float* __rest
 // (the common case: L is thousands of samples) the taps are read straight, without the extension arithmetic.
 template <typename T>
 __global__ void __launch_bounds__(kBlock) dwt1_fwd_kernel(const T* __restrict__ x, T* __restrict__ lo, T* __restrict__ hi,
-                                                           int64_t rows, int L, int n, Taps<T> tp, int mode) {
+                                                           int64_t rows, int L, int n, LongTaps<T> tp, int mode) {
     kernarg_touch_for(x, lo, hi, rows, L, n, tp, mode);
     const int64_t total = rows * n;
     const int F = tp.len;
@@ -197,7 +197,7 @@ __global__ void __launch_bounds__(kBlock) dwt1_fwd_kernel(const T* __restrict__ 
 // periodization output costs F / 2 terms like the others (synth() above scans all n coefficients in that mode)
 template <typename T>
 __global__ void __launch_bounds__(kBlock) dwt1_inv_kernel(const T* __restrict__ lo, int lo_len, const T* __restrict__ hi,
-                                                           T* __restrict__ out, int64_t rows, int n, int Lo, Taps<T> tp, int mode) {
+                                                           T* __restrict__ out, int64_t rows, int n, int Lo, LongTaps<T> tp, int mode) {
     kernarg_touch_for(lo, lo_len, hi, out, rows, n, Lo, tp, mode);
     const int64_t total = rows * Lo;
     const int F = tp.len;
@@ -227,11 +227,14 @@ static int dwt2_fwd(const T* x, T* ll, T* hi, int64_t planes, int64_t H, int64_t
                     int flen, int mode, void* ws, hipStream_t st, const char* what) {
     SONAR_REQUIRE(x && ll && hi && ws && planes >= 0 && mode >= 0 && mode <= 5, SONAR_ERR_ARG, "%s: bad argument", what);
     SONAR_REQUIRE(dims_ok(H, W), SONAR_ERR_UNSUPPORTED, "%s: bad plane size", what);
-    Taps<T> tp;
+    LongTaps<T> tp;
     SONAR_REQUIRE(make_taps(tp, dec_lo, dec_hi, flen), SONAR_ERR_ARG, "%s: 1..%d filter taps required", what, kMaxTaps);
     if (planes == 0) return SONAR_OK;
     const int h = (int)dwt_len(H, flen, mode), w = (int)dwt_len(W, flen, mode);
-    if (dwt2_fwd_tiled<T>(x, ll, hi, planes, (int)H, (int)W, h, w, tp, mode, st)) return check_launch(what);  // LDS-staged, one launch
+    Taps<T> tile_tp;  // the tile kernels keep their own, shorter argument block
+    if (tile_taps_ok(flen) && make_taps(tile_tp, dec_lo, dec_hi, flen) &&
+        dwt2_fwd_tiled<T>(x, ll, hi, planes, (int)H, (int)W, h, w, tile_tp, mode, st))
+        return check_launch(what);  // LDS-staged, one launch
     T* tmp = (T*)ws;
     hipLaunchKernelGGL((dwt_rows_kernel<T>), dim3(grid_for(planes * H * w, kBlock)), dim3(kBlock), 0, st, x, tmp, planes * H, (int)W, w,
                        tp, mode);
@@ -246,7 +249,7 @@ static int dwt2_inv(const T* ll, int64_t ll_h, int64_t ll_w, const T* hi, T* out
                     const char* what) {
     SONAR_REQUIRE(ll && hi && out && ws && planes >= 0 && mode >= 0 && mode <= 5, SONAR_ERR_ARG, "%s: bad argument", what);
     SONAR_REQUIRE(dims_ok(h, w) && ll_h >= h && ll_w >= w, SONAR_ERR_ARG, "%s: bad coefficient size", what);
-    Taps<T> tp;
+    LongTaps<T> tp;
     SONAR_REQUIRE(make_taps(tp, rec_lo, rec_hi, flen), SONAR_ERR_ARG, "%s: 1..%d filter taps required", what, kMaxTaps);
     const int64_t Hr = mode == kPeriodization ? 2 * h : 2 * h - flen + 2;
     const int64_t Wr = mode == kPeriodization ? 2 * w : 2 * w - flen + 2;
@@ -254,7 +257,10 @@ static int dwt2_inv(const T* ll, int64_t ll_h, int64_t ll_w, const T* hi, T* out
                   "%s: requested output %lldx%lld exceeds the reconstruction %lldx%lld", what, (long long)Ho, (long long)Wo,
                   (long long)Hr, (long long)Wr);
     if (planes == 0) return SONAR_OK;
-    if (dwt2_inv_tiled<T>(ll, (int)ll_h, (int)ll_w, hi, out, planes, (int)h, (int)w, (int)Ho, (int)Wo, tp, mode, st)) return check_launch(what);
+    Taps<T> tile_tp;
+    if (tile_taps_ok(flen) && make_taps(tile_tp, rec_lo, rec_hi, flen) &&
+        dwt2_inv_tiled<T>(ll, (int)ll_h, (int)ll_w, hi, out, planes, (int)h, (int)w, (int)Ho, (int)Wo, tile_tp, mode, st))
+        return check_launch(what);
     T* tmp = (T*)ws;
     hipLaunchKernelGGL((idwt_cols_kernel<T>), dim3(grid_for(planes * Hr * w, kBlock)), dim3(kBlock), 0, st, ll, (int)ll_h, (int)ll_w, hi,
                        tmp, planes, (int)h, (int)w, (int)Hr, tp, mode);
@@ -268,7 +274,7 @@ static int dwt1_fwd(const T* x, T* lo, T* hi, int64_t rows, int64_t L, const dou
                     hipStream_t st, const char* what) {
     SONAR_REQUIRE(x && lo && hi && rows >= 0 && mode >= 0 && mode <= 5, SONAR_ERR_ARG, "%s: bad argument", what);
     SONAR_REQUIRE(L > 0 && L < (1 << 30), SONAR_ERR_UNSUPPORTED, "%s: bad signal length", what);
-    Taps<T> tp;
+    LongTaps<T> tp;
     SONAR_REQUIRE(make_taps(tp, dec_lo, dec_hi, flen), SONAR_ERR_ARG, "%s: 1..%d filter taps required", what, kMaxTaps);
     if (rows == 0) return SONAR_OK;
     const int n = (int)dwt_len(L, flen, mode);
@@ -281,7 +287,7 @@ static int dwt1_inv(const T* lo, int64_t lo_len, const T* hi, T* out, int64_t ro
                     const double* rec_hi, int flen, int mode, hipStream_t st, const char* what) {
     SONAR_REQUIRE(lo && hi && out && rows >= 0 && mode >= 0 && mode <= 5, SONAR_ERR_ARG, "%s: bad argument", what);
     SONAR_REQUIRE(n > 0 && n < (1 << 29) && lo_len >= n, SONAR_ERR_ARG, "%s: bad coefficient length", what);
-    Taps<T> tp;
+    LongTaps<T> tp;
     SONAR_REQUIRE(make_taps(tp, rec_lo, rec_hi, flen), SONAR_ERR_ARG, "%s: 1..%d filter taps required", what, kMaxTaps);
     const int64_t Lr = mode == kPeriodization ? 2 * n : 2 * n - flen + 2;
     SONAR_REQUIRE(Lr > 0 && Lo > 0 && Lo <= Lr, SONAR_ERR_ARG, "%s: requested output %lld exceeds the reconstruction %lld", what,

@@ -5,16 +5,24 @@
 
 namespace sonar {
 
-constexpr int kMaxTaps = 64;
+constexpr int kMaxTaps = 102;      // the longest filters of the table (db38, coif17): the per-pass 2-D kernels and the 1-D kernels
+constexpr int kTileTapsCap = 64;   // slots in the argument block of the tile / fused kernels (they take at most 20 taps, tile_taps_ok)
 constexpr int kMaxLevels = 12;
 enum DwtMode { kZero = 0, kSymmetric = 1, kReflect = 2, kPeriodization = 3, kPeriodic = 4, kConstant = 5 };
 
-template <typename T>
-struct Taps {
-    T lo[kMaxTaps];
-    T hi[kMaxTaps];
+template <typename T, int CAP>
+struct TapsOf {
+    static constexpr int kCap = CAP;
+    T lo[CAP];
+    T hi[CAP];
     int len;
 };
+template <typename T>
+using Taps = TapsOf<T, kTileTapsCap>;
+template <typename T>
+using LongTaps = TapsOf<T, kMaxTaps>;
+// the widest kernel of dwt.hip passes LongTaps<double> next to 72 bytes of other arguments; the argument block holds 4 KB
+static_assert(sizeof(LongTaps<double>) + 128 <= 4096, "LongTaps<double> and a kernel's other arguments fit the 4 KB argument block");
 
 __host__ __device__ inline int64_t dwt_len(int64_t n, int64_t flen, int mode) {
     return mode == kPeriodization ? (n + 1) / 2 : (n + flen - 1) / 2;
@@ -48,9 +56,9 @@ __device__ __forceinline__ int ext_index(int idx, int n, int mode) {
 }
 
 // one synthesis output from two coefficient sequences a (stride sa) and d (stride sd)
-template <typename T>
+template <typename T, typename TP>
 __device__ __forceinline__ T synth(const T* __restrict__ a, int64_t sa, const T* __restrict__ d, int64_t sd, int n, int o,
-                                   const Taps<T>& tp, int mode) {
+                                   const TP& tp, int mode) {
     const int F = tp.len;
     T acc = T(0);
     if (mode == kPeriodization) {
@@ -93,11 +101,11 @@ __device__ __forceinline__ T band_combine(T c, T u, const BandScales<T>& sc, int
     return r;
 }
 
-template <typename T>
-static bool make_taps(Taps<T>& tp, const double* lo, const double* hi, int flen) {
-    if (!lo || !hi || flen < 1 || flen > kMaxTaps) return false;
+template <typename T, int CAP>
+static bool make_taps(TapsOf<T, CAP>& tp, const double* lo, const double* hi, int flen) {
+    if (!lo || !hi || flen < 1 || flen > CAP) return false;
     tp.len = flen;
-    for (int j = 0; j < kMaxTaps; ++j) {
+    for (int j = 0; j < CAP; ++j) {
         tp.lo[j] = j < flen ? (T)lo[j] : T(0);
         tp.hi[j] = j < flen ? (T)hi[j] : T(0);
     }

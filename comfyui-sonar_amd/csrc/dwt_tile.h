@@ -678,10 +678,12 @@ static int wcfg_fused(const float* cond, const float* uncond, const float* x, fl
                       mode_fwd <= 5 && mode_inv >= 0 && mode_inv <= 5 && blend_mode >= 0 && blend_mode <= 2,
                   SONAR_ERR_ARG, "%s: bad argument", what);
     SONAR_REQUIRE(dims_ok(H, W), SONAR_ERR_UNSUPPORTED, "%s: bad plane size", what);
+    // refused before the taps are copied: a longer filter (up to kMaxTaps) is the per-pass kernels' business, and the caller's fallback
+    SONAR_REQUIRE(dec_len < 1 || rec_len < 1 || (tile_taps_ok(dec_len) && tile_taps_ok(rec_len)), SONAR_ERR_UNSUPPORTED,
+                  "%s: even filter lengths 2..20 only", what);
     Taps<T> dec, rec;
     SONAR_REQUIRE(make_taps(dec, dec_lo, dec_hi, dec_len) && make_taps(rec, rec_lo, rec_hi, rec_len), SONAR_ERR_ARG,
-                  "%s: 1..%d filter taps required", what, kMaxTaps);
-    SONAR_REQUIRE(tile_taps_ok(dec_len) && tile_taps_ok(rec_len), SONAR_ERR_UNSUPPORTED, "%s: even filter lengths 2..20 only", what);
+                  "%s: 1..%d filter taps required", what, kTileTapsCap);
     // difference-only rule over a perfect-reconstruction pair (the caller vouches for the pair: one wavelet both ways): every cond /
     // uncond / final scale is 1, the blend is linear in (uncond band, difference band), so
     //   IDWT(blend(U, D (C - U), t)) = ku u + kt IDWT(D DWT(c - u))

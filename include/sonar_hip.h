@@ -956,7 +956,9 @@ int sonar_channel_mix_f32(const float* in, const float* mixer, float* out, int64
 /* pytorch_wavelets DWTForward/DWTInverse semantics == pywt.dwt2/idwt2 per level
  * (py/wavelet_functions.py:56-105).  One level per call; the host loops levels.
  *   mode: 0 zero, 1 symmetric, 2 reflect, 3 periodization, 4 periodic(ppd), 5 constant(replicate)
- *   dec_lo/dec_hi (rec_lo/rec_hi): HOST arrays of `flen` (<= 64) taps in pywt order
+ *   dec_lo/dec_hi (rec_lo/rec_hi): HOST arrays of `flen` (1 .. 102: every wavelet of the table, db38 and coif17 included)
+ *             taps in pywt order; more is SONAR_ERR_ARG "1..102 filter taps required".  Even lengths up to 20 on planes
+ *             that fit a 64 KiB LDS tile run in one LDS-staged launch, everything else as a row pass and a column pass.
  *   forward : x[planes][H][W] -> ll[planes][h][w], hi[planes][3][h][w]  (orientations LH,HL,HH == pywt cH,cV,cD;
  *             h = sonar_dwt_out_len(H), w = sonar_dwt_out_len(W))
  *   inverse : ll[planes][ll_h][ll_w] (only its leading h x w block is used: pytorch_wavelets drops the extra
