@@ -6,6 +6,9 @@
 //                          index of the smallest and, for softmin, the online-softmax sums) -- registers only, every array below is indexed
 //                          by an unrolled constant.  The epilogue evaluates the result terms and does out = out + result * amplitude (and
 //                          the generator's final division after the last octave).
+//   voronoi_rank_kernel    the rank route (sonar_voronoi_rank_octave_f32): the same pixel, staging and distance program, but any order
+//                          statistic of the row -- the k-th smallest by a bit-by-bit search on the ordered-integer image of the floats,
+//                          32 counting sweeps over the points -- and softmin:use_sorted on a row held in LDS.
 // The grid, the two `% 1` and the wrap are the reference's fp32 operations one rounding each (__fmul_rn / __fadd_rn / __fdiv_rn and the
 // library's -ffp-contract=off), so a difference lands on the side of the wrap where the reference's lands.  Square roots are sqrtf, the
 // correctly rounded one (the __fsqrt_rn of this toolchain is the native instruction, 1 ulp).
@@ -274,6 +277,230 @@ __global__ void __launch_bounds__(kBlock) voronoi_octave_kernel(const float* __r
     }
 }
 
+// ---- the rank route: order statistics anywhere in the sorted row (py/noise_generation.py:1606-1704)
+constexpr int kRowLanes = 64;                       // the ROW instantiation's workgroup: one wave, its distance rows side by side in LDS
+constexpr int kRowN = SONAR_VORONOI_RANK_ROW_N;     // the longest row softmin:use_sorted is built for
+static_assert(kRowN <= kChunk, "the ROW instantiation reads every point of the plane from one staged chunk");
+static_assert((3 * kChunk + kRowLanes * kRowN) * sizeof(float) <= 160 * 1024, "the staged points and a wave's rows fit the CU's LDS");
+
+struct FuzzPixel {  // what voronoi_octave_kernel's pass 2 keeps per launch and per pixel
+    float gmin = 0.0f, gmax = 0.0f, span = 0.0f, fz1 = 0.0f, fz2 = 0.0f, rlo = 0.0f, rhi = 0.0f;
+};
+
+// the distance expression of one point, voronoi_octave_kernel's own steps (PASS -1 without a fuzz term, PASS 2 with one)
+template <bool FUZZ>
+__device__ __forceinline__ float rank_distance(const sonar_voronoi_program& prog, int n_d, const FuzzArgs& fz, const FuzzPixel px, float& u0, float& u1,
+                                               float& u2, float& u3, int64_t& have, float d0, float d1, float d2, int64_t elem, bool live) {
+    float dist = 0.0f;
+#pragma unroll
+    for (int t = 0; t < kTerms; ++t) {
+        if (t >= n_d) break;
+        float v = distance_term<false>(prog.d[t], d0, d1, d2);
+        if constexpr (FUZZ) {
+            if (t == fz.term && live) {
+                float u;
+                if (fz.u != nullptr) {
+                    u = fz.u[elem];
+                } else {
+                    const int64_t e = fz.elem_offset + elem;
+                    if ((e >> 2) != have) have = e >> 2, stream_uniform4(fz.seed, fz.stream_id, e & ~(int64_t)3, u0, u1, u2, u3);
+                    const float lo = (e & 1) ? u1 : u0, hi = (e & 1) ? u3 : u2;  // (two selects: a chain over the slot becomes an indexed array)
+                    u = (e & 2) ? hi : lo;
+                }
+                v = __fadd_rn(v, __fsub_rn(__fmul_rn(u, px.fz2), px.fz1));
+                v = minmax_rescale_value(v, px.rlo, px.rhi, 1e-07f, px.gmin, px.gmax, px.span);
+            }
+        }
+        v = __fmul_rn(v, prog.d[t].scale);
+        dist = t == 0 ? v : __fadd_rn(dist, v);
+    }
+    return dist;
+}
+
+// the result fractal_norm chain of term r on the distance
+__device__ __forceinline__ float rank_value(const sonar_voronoi_rterm& r, float e) {
+#pragma unroll
+    for (int k = 0; k < kChain; ++k) {
+        if (k >= r.n_fn) break;
+        const float a = __fmul_rn(e, r.fb[k]);
+        e = __fmul_rn(r.fa[k], r.fn[k] == SONAR_VORONOI_X_FRACTAL_SIN ? sinf(a) : cosf(a));
+    }
+    return e;
+}
+
+__device__ __forceinline__ float softmin_logit(float gy, float gx, float gz, const float* p, float temperature) {
+    const float d0 = wrap_diff(gy, p[0]), d1 = wrap_diff(gx, p[1]), d2 = wrap_diff(gz, p[2]);
+    return __fmul_rn(-sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2))), temperature);
+}
+
+// One thread per pixel as above, but the selection is exact for any rank: the k-th smallest value of a pixel's row is the largest v with
+// #{e_j < v} <= k, found bit by bit on the ordered-integer image of the floats -- 32 sweeps over the points, each counting for both
+// ranks of every term at once, registers only (tied values are equal, so ties need no rule).  A sweep before them (`stats`) keeps what
+// the other ops need: softmin's online sums, the index of the smallest, the largest logit.  Terms do not share a sorted tensor here: an F
+// term is a value (the median is one), and the host keeps sums that hold a bare f view of the reference on the top-four route.
+// ROW (a workgroup of one wave, N <= kRowN): softmin:use_sorted pairs the weight of point j with the j-th smallest value, which is
+// sum_i e_i w[rank(i)], rank(i) = #{j : e_j < e_i or (e_j == e_i and j < i)}.  The pixel's row of e lies in LDS lane-major (row[j * 64 +
+// lane]: a wave's 64 lanes read 64 consecutive words), the weights are recomputed from the staged points.
+template <bool ROW, bool FUZZ>
+__global__ void __launch_bounds__(ROW ? kRowLanes : kBlock) voronoi_rank_kernel(const float* __restrict__ fp, float* __restrict__ out,
+                                                                                const float* __restrict__ aux, int64_t planes, int H, int W, int N,
+                                                                                float scale, float z_norm, float amplitude, float final_div,
+                                                                                int flags, sonar_voronoi_program prog, FuzzArgs fz) {
+    constexpr int BLOCK = ROW ? kRowLanes : kBlock;
+    extern __shared__ float rank_lds[];
+    float* pts = rank_lds;               // 3 * kChunk
+    float* row = rank_lds + 3 * kChunk;  // ROW: kRowLanes * N
+    const int hw = H * W;
+    const int tiles = (hw + BLOCK - 1) / BLOCK;
+    const int64_t work = planes * tiles;
+    const float gz = rem1(__fmul_rn(z_norm, scale));
+    const int n_d = prog.n_d, n_r = prog.n_r;
+    bool stats = false, select = false;
+#pragma unroll
+    for (int t = 0; t < kTerms; ++t) {
+        if (t >= n_r) break;
+        if (prog.r[t].op <= SONAR_VORONOI_R_DIFF2) select = true;
+        else stats = true;
+    }
+    FuzzPixel px;
+    if constexpr (FUZZ) {
+        px.gmin = unordered(fz.stats[0]), px.gmax = unordered(fz.stats[1]);
+        const double f = fmax(fabs((double)px.gmin), fabs((double)px.gmax)) * fz.fuzz;
+        px.fz1 = (float)f, px.fz2 = (float)(f * 2.0);
+        px.span = (float)((double)px.gmax - (double)px.gmin);
+    }
+    for (int64_t unit = blockIdx.x; unit < work; unit += gridDim.x) {  // (uniform: every thread reaches the barriers below)
+        const int64_t plane = unit / tiles;
+        const int pix = (int)(unit - plane * tiles) * BLOCK + (int)threadIdx.x;
+        const bool live = pix < hw;
+        const int y = live ? pix / W : 0, x = live ? pix - y * W : 0;
+        const float gy = rem1(__fmul_rn(__fdiv_rn((float)y, (float)H), scale));
+        const float gx = rem1(__fmul_rn(__fdiv_rn((float)x, (float)W), scale));
+        const float* plane_pts = fp + plane * (int64_t)N * 3;
+        const int64_t flat = (plane * hw + pix) * (int64_t)N;
+        float u0 = 0.0f, u1 = 0.0f, u2 = 0.0f, u3 = 0.0f;
+        int64_t have = -1;  // the group of four stream elements u0..u3 hold
+        if constexpr (FUZZ) {
+            const int64_t r = plane * H + y;
+            if (live) px.rlo = unordered(fz.stats[2 + 2 * r]), px.rhi = unordered(fz.stats[3 + 2 * r]);
+        }
+        uint32_t c1[kTerms], c2[kTerms];  // the ordered images of the idx1-th and idx2-th smallest, built from the top bit down
+        float m0[kTerms], smax[kTerms], ssum[kTerms], sacc[kTerms];
+        int arg[kTerms];
+#pragma unroll
+        for (int t = 0; t < kTerms; ++t) c1[t] = c2[t] = 0u, m0[t] = INFINITY, smax[t] = -INFINITY, ssum[t] = 0.0f, sacc[t] = 0.0f, arg[t] = 0;
+        for (int sweep = stats ? -1 : 0; sweep < (select ? 32 : 0); ++sweep) {
+            const uint32_t bit = sweep < 0 ? 0u : 0x80000000u >> sweep;
+            int n1[kTerms], n2[kTerms];
+#pragma unroll
+            for (int t = 0; t < kTerms; ++t) n1[t] = n2[t] = 0;
+            for (int base = 0; base < N; base += kChunk) {
+                const int cnt = N - base < kChunk ? N - base : kChunk;
+                __syncthreads();  // the previous chunk has been read
+                for (int i = (int)threadIdx.x; i < cnt; i += BLOCK) {
+                    const float* p = plane_pts + (int64_t)(base + i) * 3;
+                    pts[3 * i + 0] = rem1(__fmul_rn(p[0], scale));
+                    pts[3 * i + 1] = rem1(__fmul_rn(p[1], scale));
+                    pts[3 * i + 2] = rem1(__fmul_rn(p[2], scale));
+                }
+                __syncthreads();
+                for (int j = 0; j < cnt; ++j) {
+                    const float d0 = wrap_diff(gy, pts[3 * j + 0]), d1 = wrap_diff(gx, pts[3 * j + 1]), d2 = wrap_diff(gz, pts[3 * j + 2]);
+                    const float dist = rank_distance<FUZZ>(prog, n_d, fz, px, u0, u1, u2, u3, have, d0, d1, d2, flat + base + j, live);
+#pragma unroll
+                    for (int t = 0; t < kTerms; ++t) {
+                        if (t >= n_r) break;
+                        const sonar_voronoi_rterm& r = prog.r[t];
+                        const float e = rank_value(r, dist);
+                        if (sweep >= 0) {
+                            const uint32_t key = ordered(e);
+                            n1[t] += key < (c1[t] | bit) ? 1 : 0;
+                            n2[t] += key < (c2[t] | bit) ? 1 : 0;
+                        } else if (r.op == SONAR_VORONOI_R_SOFTMIN || r.op == SONAR_VORONOI_R_SOFTMIN_SORTED) {
+                            const float norm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+                            const float logit = __fmul_rn(-norm, r.temperature);
+                            const float top = fmaxf(smax[t], logit);
+                            const float keep = expf(__fsub_rn(smax[t], top)), w = expf(__fsub_rn(logit, top));  // the first point: exp(-inf) = 0
+                            ssum[t] = __fadd_rn(__fmul_rn(ssum[t], keep), w);
+                            sacc[t] = __fadd_rn(__fmul_rn(sacc[t], keep), __fmul_rn(e, w));
+                            smax[t] = top;
+                        } else {  // the first index of the smallest
+                            arg[t] = e < m0[t] ? base + j : arg[t];
+                            m0[t] = fminf(m0[t], e);
+                        }
+                    }
+                }
+            }
+            if (sweep >= 0) {
+#pragma unroll
+                for (int t = 0; t < kTerms; ++t) {
+                    if (t >= n_r) break;
+                    c1[t] |= n1[t] <= prog.r[t].idx1 ? bit : 0u;
+                    c2[t] |= n2[t] <= prog.r[t].idx2 ? bit : 0u;
+                }
+            }
+        }
+        if constexpr (ROW) {  // (N <= kChunk: the last sweep left every point of the plane staged)
+#pragma unroll
+            for (int t = 0; t < kTerms; ++t) {
+                if (t >= n_r) break;
+                const sonar_voronoi_rterm& r = prog.r[t];
+                if (r.op != SONAR_VORONOI_R_SOFTMIN_SORTED) continue;
+                float* mine = row + threadIdx.x;
+                float total = 0.0f;  // the softmax denominator, the weights' exponentials in index order
+                for (int j = 0; j < N; ++j) {
+                    const float d0 = wrap_diff(gy, pts[3 * j + 0]), d1 = wrap_diff(gx, pts[3 * j + 1]), d2 = wrap_diff(gz, pts[3 * j + 2]);
+                    mine[j * kRowLanes] = rank_value(r, rank_distance<FUZZ>(prog, n_d, fz, px, u0, u1, u2, u3, have, d0, d1, d2, flat + j, live));
+                    total = __fadd_rn(total, expf(__fsub_rn(softmin_logit(gy, gx, gz, pts + 3 * j, r.temperature), smax[t])));
+                }
+                float acc = 0.0f;
+                for (int i = 0; i < N; ++i) {
+                    const float ei = mine[i * kRowLanes];
+                    int rank = 0;
+                    for (int j = 0; j < N; ++j) {
+                        const float ej = mine[j * kRowLanes];
+                        rank += (ej < ei || (ej == ei && j < i)) ? 1 : 0;
+                    }
+                    const float w = __fdiv_rn(expf(__fsub_rn(softmin_logit(gy, gx, gz, pts + 3 * rank, r.temperature), smax[t])), total);
+                    acc = __fadd_rn(acc, __fmul_rn(ei, w));
+                }
+                sacc[t] = acc, ssum[t] = 1.0f;
+            }
+        }
+        float result = 0.0f;
+#pragma unroll
+        for (int t = 0; t < kTerms; ++t) {
+            if (t >= n_r) break;
+            const sonar_voronoi_rterm& r = prog.r[t];
+            const float v1 = unordered(c1[t]), v2 = unordered(c2[t]);
+            float v;
+            switch (r.op) {
+                case SONAR_VORONOI_R_F: v = v1; break;
+                case SONAR_VORONOI_R_INV_F: v = __fdiv_rn(1.0f, __fadd_rn(v1, r.eps)); break;
+                case SONAR_VORONOI_R_DIFF: v = __fsub_rn(v2, v1); break;
+                case SONAR_VORONOI_R_DIFF2: v = __fdiv_rn(__fsub_rn(v2, v1), __fadd_rn(__fadd_rn(v2, v1), 1e-06f)); break;
+                case SONAR_VORONOI_R_SOFTMIN:
+                case SONAR_VORONOI_R_SOFTMIN_SORTED: v = __fdiv_rn(sacc[t], ssum[t]); break;
+                case SONAR_VORONOI_R_CELLID: v = __fadd_rn(__fdiv_rn((float)arg[t], aux[t]), 1.0f); break;
+                default: v = (float)arg[t]; break;
+            }
+#pragma unroll
+            for (int k = 0; k < kChain; ++k) {
+                if (k >= r.n_ridge) break;
+                v = __fsub_rn(1.0f, __fmul_rn(r.ridge[k], v));
+            }
+            v = __fmul_rn(v, r.scale);
+            result = t == 0 ? v : __fadd_rn(result, v);
+        }
+        if (live) {
+            const int64_t at = plane * hw + pix;
+            float o = __fadd_rn(out[at], __fmul_rn(result, amplitude));
+            if (flags & SONAR_VORONOI_FINAL_DIV) o = __fdiv_rn(o, final_div);
+            out[at] = o;
+        }
+    }
+}
+
 // gradient_magnitude (py/noise_generation.py:1706-1724) on two planes of inner results, replicate padding by clamped indices:
 // acc += sqrt(dx^2 + dy^2) * scale, dx = r1[y][x + 1] - r2[y][x - 1], dy = r1[y + 1][x] - r2[y - 1][x]
 __global__ void __launch_bounds__(kBlock) voronoi_gradient_kernel(const float* __restrict__ r1, const float* __restrict__ r2, float* __restrict__ acc,
@@ -310,12 +537,13 @@ __global__ void __launch_bounds__(kBlock) voronoi_acc_kernel(float* __restrict__
 
 }  // namespace sonar
 
-// the checks and the launch both octave entry points share; fz NULL (pass -1): no fuzz term
-static int voronoi_octave(const char* who, const float* fp, float* out, const float* aux, int64_t B, int64_t C, int64_t H, int64_t W, int64_t N,
-                          float scale, float z_norm, float amplitude, float final_div, int flags, const sonar_voronoi_program* prog,
-                          const sonar::FuzzArgs* fz, int pass, void* stream) {
+// the checks every octave entry point shares (pass 0 and 1 of the fuzz entry take no output); rank: the rank route's ops, and its ranks
+// are held to [0, N) by the entry point itself.  *launch: there are pixels to compute
+static int voronoi_checks(const char* who, const float* fp, float* out, const float* aux, int64_t B, int64_t C, int64_t H, int64_t W, int64_t N,
+                          int flags, const sonar_voronoi_program* prog, int pass, bool rank, bool* launch) {
     using namespace sonar;
     constexpr int64_t kMax = (int64_t)1 << 31;
+    *launch = false;
     SONAR_REQUIRE(fp != nullptr && (out != nullptr || pass == 0 || pass == 1) && prog != nullptr, SONAR_ERR_ARG, "%s: NULL tensor or program", who);
     SONAR_REQUIRE((const void*)out != (const void*)fp, SONAR_ERR_ARG, "%s: out must not be fp", who);
     SONAR_REQUIRE(aux == nullptr || ((const void*)aux != (const void*)out), SONAR_ERR_ARG, "%s: out must not be aux", who);
@@ -338,9 +566,10 @@ static int voronoi_octave(const char* who, const float* fp, float* out, const fl
     }
     for (int t = 0; t < prog->n_r; ++t) {
         const sonar_voronoi_rterm& r = prog->r[t];
-        SONAR_REQUIRE(r.op >= SONAR_VORONOI_R_F && r.op <= SONAR_VORONOI_R_CELLID_RAW, SONAR_ERR_ARG, "%s: result term %d: unknown op %d", who, t, r.op);
-        SONAR_REQUIRE(r.idx1 >= 0 && r.idx1 <= 3 && r.idx2 >= 0 && r.idx2 <= 3, SONAR_ERR_ARG, "%s: result term %d: idx (%d, %d) outside 0..3", who, t,
-                      r.idx1, r.idx2);
+        SONAR_REQUIRE(r.op >= SONAR_VORONOI_R_F && r.op <= (rank ? SONAR_VORONOI_R_SOFTMIN_SORTED : SONAR_VORONOI_R_CELLID_RAW), SONAR_ERR_ARG,
+                      "%s: result term %d: unknown op %d", who, t, r.op);
+        SONAR_REQUIRE(rank || (r.idx1 >= 0 && r.idx1 <= 3 && r.idx2 >= 0 && r.idx2 <= 3), SONAR_ERR_ARG,
+                      "%s: result term %d: idx (%d, %d) outside 0..3", who, t, r.idx1, r.idx2);
         SONAR_REQUIRE(r.n_fn >= 0 && r.n_fn <= SONAR_VORONOI_MAX_CHAIN && r.n_ridge >= 0 && r.n_ridge <= SONAR_VORONOI_MAX_CHAIN, SONAR_ERR_ARG,
                       "%s: result term %d: chains of %d and %d", who, t, r.n_fn, r.n_ridge);
         for (int k = 0; k < r.n_fn; ++k)
@@ -354,6 +583,18 @@ static int voronoi_octave(const char* who, const float* fp, float* out, const fl
     SONAR_REQUIRE(N >= 2, SONAR_ERR_ARG, "%s: %lld feature points (at least 2)", who, (long long)N);
     SONAR_REQUIRE(N <= SONAR_VORONOI_MAX_POINTS, SONAR_ERR_UNSUPPORTED, "%s: %lld feature points (at most %d)", who, (long long)N,
                   SONAR_VORONOI_MAX_POINTS);
+    *launch = true;
+    return SONAR_OK;
+}
+
+// the checks and the launch the two top-four entry points share; fz NULL (pass -1): no fuzz term
+static int voronoi_octave(const char* who, const float* fp, float* out, const float* aux, int64_t B, int64_t C, int64_t H, int64_t W, int64_t N,
+                          float scale, float z_norm, float amplitude, float final_div, int flags, const sonar_voronoi_program* prog,
+                          const sonar::FuzzArgs* fz, int pass, void* stream) {
+    using namespace sonar;
+    bool launch = false;
+    const int rc = voronoi_checks(who, fp, out, aux, B, C, H, W, N, flags, prog, pass, false, &launch);
+    if (rc != SONAR_OK || !launch) return rc;
     const int64_t planes = B * C, tiles = (H * W + kBlock - 1) / kBlock;
     const dim3 grid(grid_for(planes * tiles * kBlock, kBlock)), block(kBlock);
     const bool simple = fz == nullptr && prog->n_d == 1 && prog->n_r == 1 && prog->d[0].n_xform == 0 && prog->r[0].n_fn == 0;
@@ -382,12 +623,10 @@ extern "C" int sonar_voronoi_octave_f32(const float* fp, float* out, const float
                           stream);
 }
 
-extern "C" int sonar_voronoi_fuzz_octave_f32(const float* fp, float* out, const float* aux, const float* u, uint32_t* stats, int64_t B, int64_t C,
-                                             int64_t H, int64_t W, int64_t N, float scale, float z_norm, float amplitude, float final_div,
-                                             int flags, const sonar_voronoi_program* prog, int pass, int fuzz_term, double fuzz, uint64_t seed,
-                                             uint64_t stream_id, int64_t elem_offset, void* stream) {
+// what the fuzz distance term's arguments must satisfy, for both entry points that take one
+static int voronoi_fuzz_checks(const char* who, const float* fp, const float* out, const float* u, const uint32_t* stats,
+                               const sonar_voronoi_program* prog, int pass, int fuzz_term, double fuzz, uint64_t stream_id, int64_t elem_offset) {
     using namespace sonar;
-    const char* who = "sonar_voronoi_fuzz_octave_f32";
     SONAR_REQUIRE(stats != nullptr, SONAR_ERR_ARG, "%s: NULL stats", who);
     SONAR_REQUIRE((const void*)stats != (const void*)out && (const void*)stats != (const void*)fp && (const void*)stats != (const void*)u &&
                       (u == nullptr || (const void*)u != (const void*)out),
@@ -398,8 +637,70 @@ extern "C" int sonar_voronoi_fuzz_octave_f32(const float* fp, float* out, const 
     SONAR_REQUIRE(elem_offset >= 0 && elem_offset < ((int64_t)1 << 48) && stream_id < ((uint64_t)1 << 48), SONAR_ERR_ARG,
                   "%s: elem_offset %lld or the stream id outside [0, 2^48)", who, (long long)elem_offset);
     // (the flat index stays below 2^31 outputs x 4096 points, the stream element below that plus 2^48)
+    return SONAR_OK;
+}
+
+extern "C" int sonar_voronoi_fuzz_octave_f32(const float* fp, float* out, const float* aux, const float* u, uint32_t* stats, int64_t B, int64_t C,
+                                             int64_t H, int64_t W, int64_t N, float scale, float z_norm, float amplitude, float final_div,
+                                             int flags, const sonar_voronoi_program* prog, int pass, int fuzz_term, double fuzz, uint64_t seed,
+                                             uint64_t stream_id, int64_t elem_offset, void* stream) {
+    using namespace sonar;
+    const char* who = "sonar_voronoi_fuzz_octave_f32";
+    const int rc = voronoi_fuzz_checks(who, fp, out, u, stats, prog, pass, fuzz_term, fuzz, stream_id, elem_offset);
+    if (rc != SONAR_OK) return rc;
     const FuzzArgs fz{u, stats, fuzz, fuzz_term, seed, stream_id, elem_offset};
     return voronoi_octave(who, fp, out, aux, B, C, H, W, N, scale, z_norm, amplitude, final_div, flags, prog, &fz, pass, stream);
+}
+
+extern "C" int sonar_voronoi_rank_octave_f32(const float* fp, float* out, const float* aux, const float* u, uint32_t* stats, int64_t B, int64_t C,
+                                             int64_t H, int64_t W, int64_t N, float scale, float z_norm, float amplitude, float final_div,
+                                             int flags, const sonar_voronoi_program* prog, int fuzz_term, double fuzz, uint64_t seed,
+                                             uint64_t stream_id, int64_t elem_offset, void* stream) {
+    using namespace sonar;
+    const char* who = "sonar_voronoi_rank_octave_f32";
+    const bool fuzzed = fuzz_term != -1;
+    if (fuzzed) {
+        const int rc = voronoi_fuzz_checks(who, fp, out, u, stats, prog, 2, fuzz_term, fuzz, stream_id, elem_offset);
+        if (rc != SONAR_OK) return rc;
+    } else {
+        SONAR_REQUIRE(u == nullptr && stats == nullptr, SONAR_ERR_ARG, "%s: uniforms or statistics without a fuzz term", who);
+    }
+    bool launch = false;
+    const int rc = voronoi_checks(who, fp, out, aux, B, C, H, W, N, flags, prog, 2, true, &launch);
+    if (rc != SONAR_OK) return rc;
+    bool row = false;
+    for (int t = 0; t < prog->n_r; ++t) {
+        const sonar_voronoi_rterm& r = prog->r[t];
+        SONAR_REQUIRE(r.idx1 >= 0 && r.idx2 >= 0, SONAR_ERR_ARG, "%s: result term %d: ranks (%d, %d) below 0", who, t, r.idx1, r.idx2);
+        row = row || r.op == SONAR_VORONOI_R_SOFTMIN_SORTED;
+    }
+    if (!launch) return SONAR_OK;
+    for (int t = 0; t < prog->n_r; ++t)
+        SONAR_REQUIRE(prog->r[t].idx1 < N && prog->r[t].idx2 < N, SONAR_ERR_ARG, "%s: result term %d: ranks (%d, %d) of %lld points", who, t,
+                      prog->r[t].idx1, prog->r[t].idx2, (long long)N);
+    SONAR_REQUIRE(!row || N <= SONAR_VORONOI_RANK_ROW_N, SONAR_ERR_UNSUPPORTED, "%s: softmin:use_sorted on %lld feature points (at most %d)", who,
+                  (long long)N, SONAR_VORONOI_RANK_ROW_N);
+    const int64_t planes = B * C;
+    const int per = row ? kRowLanes : kBlock;
+    const int64_t tiles = (H * W + per - 1) / per;
+    const dim3 grid(grid_for(planes * tiles * per, per)), block(per);
+    const size_t lds = (size_t)(3 * kChunk + (row ? kRowLanes * (int)N : 0)) * sizeof(float);
+    const FuzzArgs fz{u, stats, fuzz, fuzz_term, seed, stream_id, elem_offset};
+#define SONAR_VORONOI_RANK_LAUNCH(ROW, FUZZ)                                                                                                  \
+    do {                                                                                                                                      \
+        if (ROW) lds_attr(reinterpret_cast<const void*>(voronoi_rank_kernel<ROW, FUZZ>), (int)((3 * kChunk + kRowLanes * kRowN) * sizeof(float))); \
+        hipLaunchKernelGGL((voronoi_rank_kernel<ROW, FUZZ>), grid, block, lds, (hipStream_t)stream, fp, out, aux, planes, (int)H, (int)W, (int)N, \
+                           scale, z_norm, amplitude, final_div, flags, *prog, fz);                                                            \
+    } while (0)
+    if (row) {
+        if (fuzzed) SONAR_VORONOI_RANK_LAUNCH(true, true);
+        else SONAR_VORONOI_RANK_LAUNCH(true, false);
+    } else {
+        if (fuzzed) SONAR_VORONOI_RANK_LAUNCH(false, true);
+        else SONAR_VORONOI_RANK_LAUNCH(false, false);
+    }
+#undef SONAR_VORONOI_RANK_LAUNCH
+    return check_launch(who);
 }
 
 extern "C" int sonar_voronoi_gradient_f32(const float* r1, const float* r2, float* acc, int64_t planes, int64_t H, int64_t W, float scale,

@@ -207,6 +207,7 @@ SIGNATURES = {
     "sonar_collatz_mix_f32": (_I, [_P, _P, _P, _I, _I64, _I64, _I64, _I64, _F, _P]),
     "sonar_voronoi_octave_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _F, _F, _I, _P, _P]),
     "sonar_voronoi_fuzz_octave_f32": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _F, _F, _I, _P, _I, _I, _D, _U64, _U64, _I64, _P]),
+    "sonar_voronoi_rank_octave_f32": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _F, _F, _F, _I, _P, _I, _D, _U64, _U64, _I64, _P]),
     "sonar_voronoi_gradient_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _F, _P]),
     "sonar_voronoi_fuzz_add_f32": (_I, [_P, _P, _I64, _F, _F, _P]),
     "sonar_voronoi_acc_f32": (_I, [_P, _P, _I64, _F, _F, _I, _P]),
@@ -2016,7 +2017,11 @@ VORONOI_FINAL_DIV = 1                                                           
 VORONOI_METRICS = {"euclidean": 0, "manhatten": 1, "chebyshev": 2, "minkowski": 3, "quadratic": 4, "angle": 5, "angle_tanh": 6,
                    "angle_sigmoid": 7}                                                      # SONAR_VORONOI_D_*
 VORONOI_XFORMS = {"weight": 0, "fractal_sin": 1, "fractal_cos": 2}                           # SONAR_VORONOI_X_*
-VORONOI_OPS = {"f": 0, "inv_f": 1, "diff": 2, "diff2": 3, "softmin": 4, "cellid": 5, "cellid_raw": 6}  # SONAR_VORONOI_R_*
+VORONOI_OPS = {"f": 0, "inv_f": 1, "diff": 2, "diff2": 3, "softmin": 4, "cellid": 5, "cellid_raw": 6, "softmin_sorted": 7}  # SONAR_VORONOI_R_*
+VORONOI_RANK_ROW_N = 256                                                                     # SONAR_VORONOI_RANK_ROW_N
+# the rank route (sonar_voronoi_rank_octave_f32): median_distance, softmin:use_sorted and f / inv_f / diff / diff2 indices past f4 are
+# parsed and launched instead of refused; off by default, VoronoiNoiseGenerator.rank_route / parse_modes(rank=) override it per call
+VORONOI_RANK = os.environ.get("SONAR_VORONOI_RANK", "0") != "0"
 
 
 class VoronoiDTerm(C.Structure):
@@ -2104,6 +2109,33 @@ def voronoi_octave_(out: Optional[torch.Tensor], fp: torch.Tensor, prog: Voronoi
                                                 _dev(fuzz.stats, "stats", torch.int32), int(b), int(c), int(h), int(w), n, *tail, int(fuzz_pass),
                                                 fuzz.term, fuzz.fuzz, fuzz.seed, fuzz.stream_id, fuzz.elem_offset, _stream()),
            "sonar_voronoi_fuzz_octave_f32")
+    return out
+
+
+def voronoi_rank_octave_(out: torch.Tensor, fp: torch.Tensor, prog: VoronoiProgram, *, scale: float, z_norm: float, amplitude: float = 1.0,
+                         final_div: Optional[float] = None, aux: Optional[torch.Tensor] = None,
+                         fuzz: Optional[VoronoiFuzz] = None) -> torch.Tensor:
+    """sonar_voronoi_rank_octave_f32: voronoi_octave_'s contract (``out`` += octave * amplitude, then / final_div when given; in place) for
+    a program whose idx1 / idx2 are ranks anywhere in [0, N) or that holds ``softmin_sorted`` terms.  ``fuzz``: the state of a fuzz
+    distance term whose two reducing passes (voronoi_octave_, fuzz_pass 0 and 1) have run."""
+    shape = tuple(out.shape)
+    if len(shape) != 4 or fp.ndim != 4 or fp.shape[3] != 3 or tuple(fp.shape[:2]) != shape[:2]:
+        raise SonarHipError(f"voronoi_rank_octave_: feature points of shape {tuple(fp.shape)} for an output of shape {shape}")
+    if not out.is_contiguous() or not fp.is_contiguous():
+        raise SonarHipError("voronoi_rank_octave_: contiguous tensors only")
+    if aux is not None and aux.numel() < VORONOI_MAX_TERMS:
+        raise SonarHipError(f"voronoi_rank_octave_: aux holds {aux.numel()} values, {VORONOI_MAX_TERMS} are read")
+    b, c, h, w = shape
+    n = int(fp.shape[2])
+    if fuzz is not None and (fuzz.stats.numel() != 2 + 2 * b * c * h or (
+            fuzz.u is not None and (fuzz.u.numel() != b * c * h * w * n or not fuzz.u.is_contiguous()))):
+        raise SonarHipError(f"voronoi_rank_octave_: fuzz statistics of {fuzz.stats.numel()} words or uniforms that do not fit {shape} x {n}")
+    tail = (-1, 0.0, 0, 0, 0) if fuzz is None else (fuzz.term, fuzz.fuzz, fuzz.seed, fuzz.stream_id, fuzz.elem_offset)
+    _check(load().sonar_voronoi_rank_octave_f32(
+        _dev(fp, "fp"), _dev(out, "out"), _opt(aux, "aux"), None if fuzz is None else _opt(fuzz.u, "u"),
+        None if fuzz is None else _dev(fuzz.stats, "stats", torch.int32), int(b), int(c), int(h), int(w), n, float(scale), float(z_norm),
+        float(amplitude), 1.0 if final_div is None else float(final_div), 0 if final_div is None else VORONOI_FINAL_DIV, C.addressof(prog),
+        *tail, _stream()), "sonar_voronoi_rank_octave_f32")
     return out
 
 

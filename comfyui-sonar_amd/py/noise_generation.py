@@ -1105,11 +1105,18 @@ class VoronoiNoiseGenerator(NoiseGenerator):
     the real pass that rescales; nothing is read on the host and no [B, C, H, W, N] tensor is written (generate mode: the kernel computes
     the uniforms' stream elements; replay mode: the host's draw is copied over, as every replayed draw is).  Not built
     (NotImplementedError naming the expression): ``median_distance``, ``softmin:use_sorted``, ``f:idx`` outside 0..3, other ``pad_mode``s, a plane mode under another
-    wrapper, and a plane mode beside a bare ``f`` term (the reference's in-place sums alias the sorted tensor there)."""
+    wrapper, and a plane mode beside a bare ``f`` term (the reference's in-place sums alias the sorted tensor there).
+    The rank route (off by default: SONAR_VORONOI_RANK=1 in the environment, or ``rank_route = True`` on the class or an instance) builds
+    the first three: an octave whose expression reads past f4 -- ``median_distance`` (rank (n - 1) // 2), ``f`` / ``inv_f`` / ``diff`` /
+    ``diff2`` with any index Python accepts on n points (IndexError otherwise), ``softmin:use_sorted`` (n up to
+    hip_lib.VORONOI_RANK_ROW_N), also under ``ridge`` / ``fractal_norm`` and as leaves of the plane modes -- is one launch of
+    sonar_voronoi_rank_octave_f32, which finds each order statistic exactly in 32 counting sweeps over the points; every other octave
+    takes the top-four kernel as before.  Still refused there: such a term beside a bare ``f`` term in one ``+`` expression."""
 
     name = "voronoi"
     MIN_DIMS = 4
     MAX_DIMS = 4
+    rank_route = None  # the rank route's switch as parse_modes takes it: None is hip_lib.VORONOI_RANK (not a parameter: ng_params is the reference's)
 
     voronoi_distance_modes = frozenset(("angle_sigmoid", "angle_tanh", "angle", "chebyshev", "euclidean", "fractal_norm", "fuzz", "manhatten",
                                         "minkowski", "quadratic", "weight"))
@@ -1180,34 +1187,41 @@ class VoronoiNoiseGenerator(NoiseGenerator):
         return term
 
     @classmethod
-    def _parse_result(cls, name: str, kwargs: dict, fns: tuple, ridges: tuple, expr: str, top: bool = False) -> dict:
+    def _parse_result(cls, name: str, kwargs: dict, fns: tuple, ridges: tuple, expr: str, top: bool = False, rank: bool = False) -> dict:
+        """``rank``: the rank route is on -- median_distance, softmin:use_sorted and indices outside 0..3 (negative ones as written: the
+        feature set's size resolves them, _resolve) become terms instead of refusals."""
         name, kwargs = cls._mode_name(name, result=True), cls._strip(kwargs)
         if name == "median_distance":
+            if rank:
+                return {"fns": fns, "ridges": ridges, "op": "median_distance"}
             raise NotImplementedError(f"Voronoi result mode {expr!r}: {name} needs the whole sorted row per pixel")
         if name in ("fuzz", "gradient_magnitude"):
             if not top:
                 raise NotImplementedError(f"Voronoi result mode {expr!r}: {name} is built as the outermost mode of a term only")
             if name == "fuzz":
                 inner, fuzz = kwargs.pop("name", "f1"), float(kwargs.pop("fuzz", 0.25))
-                return {"op": "fuzz", "fuzz": fuzz, "inner": (cls._parse_result(inner, kwargs, (), (), expr),)}
+                return {"op": "fuzz", "fuzz": fuzz, "inner": (cls._parse_result(inner, kwargs, (), (), expr, rank=rank),)}
             name1, name2, pad_mode = kwargs.pop("name1", "f4"), kwargs.pop("name2", "f4"), kwargs.pop("pad_mode", "replicate")
             if pad_mode != "replicate":
                 raise NotImplementedError(f"Voronoi result mode {expr!r}: gradient_magnitude is built with pad_mode=replicate only")
-            first = cls._parse_result(name1, dict(kwargs), (), (), expr)
-            return {"op": "gradient_magnitude", "inner": (first,) if name2 == name1 else (first, cls._parse_result(name2, dict(kwargs), (), (), expr))}
+            first = cls._parse_result(name1, dict(kwargs), (), (), expr, rank=rank)
+            return {"op": "gradient_magnitude",
+                    "inner": (first,) if name2 == name1 else (first, cls._parse_result(name2, dict(kwargs), (), (), expr, rank=rank))}
         if name == "ridge":
             inner, exp = kwargs.pop("name", "diff"), float(kwargs.pop("exp", -10.0))
             if len(ridges) == hip_lib.VORONOI_MAX_CHAIN:
                 raise NotImplementedError(f"Voronoi result mode {expr!r}: more than {hip_lib.VORONOI_MAX_CHAIN} nested ridges")
-            return cls._parse_result(inner, kwargs, fns, (exp, *ridges), expr)
+            return cls._parse_result(inner, kwargs, fns, (exp, *ridges), expr, rank=rank)
         if name == "fractal_norm":
             inner, fn = cls._fractal(kwargs, "result", "diff")
             if len(fns) == hip_lib.VORONOI_MAX_CHAIN:
                 raise NotImplementedError(f"Voronoi result mode {expr!r}: more than {hip_lib.VORONOI_MAX_CHAIN} nested fractal_norms")
-            return cls._parse_result(inner, kwargs, (*fns, fn), ridges, expr)
+            return cls._parse_result(inner, kwargs, (*fns, fn), ridges, expr, rank=rank)
         term = {"fns": fns, "ridges": ridges}  # ridges: innermost first
         if name == "softmin":
             if kwargs.get("use_sorted") is not None:
+                if rank:
+                    return term | {"op": "softmin_sorted", "temperature": float(kwargs.get("temperature", 50.0))}
                 raise NotImplementedError(f"Voronoi result mode {expr!r}: softmin with use_sorted needs the whole sorted row per pixel")
             return term | {"op": "softmin", "temperature": float(kwargs.get("temperature", 50.0))}
         if name == "cellid":
@@ -1227,7 +1241,7 @@ class VoronoiNoiseGenerator(NoiseGenerator):
                 raise TypeError("_voronoi_result_f() got multiple values for keyword argument 'idx'")
             idxs = (int(kwargs.get("idx", 0)) if base == "f" else int(base[1:]) - 1,)
             term |= {"op": "inv_f" if inv else "f", "idx1": idxs[0], "idx2": idxs[0]}
-        if not all(0 <= i <= 3 for i in idxs):
+        if not rank and not all(0 <= i <= 3 for i in idxs):
             raise NotImplementedError(f"Voronoi result mode {expr!r}: idx outside 0..3 needs the whole sorted row per pixel")
         return term
 
@@ -1245,19 +1259,53 @@ class VoronoiNoiseGenerator(NoiseGenerator):
                 yield mode, {}, base
 
     @classmethod
-    def parse_modes(cls, distance_mode: str, result_mode: str):
-        """(distance terms, result terms) of one octave, as hip_lib.voronoi_program takes them."""
+    def parse_modes(cls, distance_mode: str, result_mode: str, rank=None):
+        """(distance terms, result terms) of one octave, as hip_lib.voronoi_program takes them.  ``rank``: whether the rank route is on
+        (None: hip_lib.VORONOI_RANK, the environment's SONAR_VORONOI_RANK); its terms still carry the indices as written and
+        ``median_distance`` as an op of its own until _resolve meets the feature set's size."""
+        rank = hip_lib.VORONOI_RANK if rank is None else bool(rank)
         dterms = [cls._parse_distance(name, kwargs, (), distance_mode, top=True) | {"scale": scale}
                   for name, kwargs, scale in cls._split_terms(distance_mode, "dscale")]
         if sum("fuzz" in d for d in dterms) > 1:
             raise NotImplementedError(f"Voronoi distance mode {distance_mode!r}: at most one fuzz term per octave expression")
-        rterms = [cls._parse_result(name, kwargs, (), (), result_mode, top=True) | {"scale": scale}
+        rterms = [cls._parse_result(name, kwargs, (), (), result_mode, top=True, rank=rank) | {"scale": scale}
                   for name, kwargs, scale in cls._split_terms(result_mode, "rscale")]
         if len(rterms) > 1 and any(cls._is_plane(r) for r in rterms) and any(
                 cls._is_view(r) or (r["op"] == "fuzz" and cls._is_view(r["inner"][0])) for r in rterms):
             raise NotImplementedError(f"Voronoi result mode {result_mode!r}: a plane mode (fuzz, gradient_magnitude) beside a bare f term -- the "
                                       "reference's in-place sums write through the sorted distances there")
+        if len(rterms) > 1 and any(cls._is_view(r) for r in rterms) and any(cls._past_f4(leaf) for leaf in cls._leaves(rterms)):
+            raise NotImplementedError(f"Voronoi result mode {result_mode!r}: an order statistic past f4 beside a bare f term -- the "
+                                      "reference's in-place sums write through the sorted distances there")
         return dterms, rterms
+
+    @classmethod
+    def _leaves(cls, rterms):
+        return [leaf for r in rterms for leaf in (r["inner"] if cls._is_plane(r) else (r,))]
+
+    @staticmethod
+    def _past_f4(term: dict) -> bool:
+        """What only the rank route computes: the median, softmin:use_sorted, an index outside 0..3 as written or a resolved median."""
+        return (term["op"] in ("median_distance", "softmin_sorted") or term.get("median", False)
+                or not (0 <= term.get("idx1", 0) <= 3 and 0 <= term.get("idx2", 0) <= 3))
+
+    @classmethod
+    def _resolve(cls, rterms, n: int, expr: str):
+        """The terms on a feature set of n points: Python's negative indices normalised and the median as rank (n - 1) // 2, torch.median's
+        lower middle value.  Terms that need neither are handed back as they are."""
+        out = []
+        for r in rterms:
+            if cls._is_plane(r):
+                r = r | {"inner": tuple(cls._resolve(r["inner"], n, expr))}
+            elif r["op"] == "median_distance":
+                r = r | {"op": "f", "idx1": (n - 1) // 2, "idx2": (n - 1) // 2, "median": True}
+            elif r["op"] == "softmin_sorted" and n > hip_lib.VORONOI_RANK_ROW_N:
+                raise NotImplementedError(f"Voronoi result mode {expr!r}: softmin with use_sorted on {n} feature points is built up to "
+                                          f"{hip_lib.VORONOI_RANK_ROW_N}")
+            elif r.get("idx1", 0) < 0 or r.get("idx2", 0) < 0:
+                r = r | {"idx1": r["idx1"] % n, "idx2": r["idx2"] % n}
+            out.append(r)
+        return out
 
     @staticmethod
     def _is_plane(term: dict) -> bool:
@@ -1278,18 +1326,21 @@ class VoronoiNoiseGenerator(NoiseGenerator):
         """(distance terms, result terms) of the octave; refuses before anything is drawn or launched."""
         key = (self.get_distance_mode(octave), self.get_result_mode(octave))
         if key not in self._programs:
-            dterms, rterms = self.parse_modes(*key)
-            leaves = [leaf for r in rterms for leaf in (r["inner"] if self._is_plane(r) else (r,))]
+            dterms, rterms = self.parse_modes(*key, rank=self.rank_route)
+            leaves = self._leaves(rterms)
             for group in ([r for r in rterms if not self._is_plane(r)], *([leaf] for leaf in leaves)):
-                if group:
-                    hip_lib.voronoi_program(dterms, group)  # the term counts
-            self._programs[key] = (dterms, rterms, max((max(r.get("idx1", 0), r.get("idx2", 0)) for r in leaves), default=0))
-        dterms, rterms, top = self._programs[key]
+                if group:  # the term counts (the median is an f term once resolved)
+                    hip_lib.voronoi_program(dterms, [r | {"op": "f"} if r["op"] == "median_distance" else r for r in group])
+            idxs = [i for r in leaves for i in (r.get("idx1", 0), r.get("idx2", 0))]
+            self._programs[key] = (dterms, rterms, max(idxs, default=0), min(idxs, default=0), {})
+        dterms, rterms, top, low, resolved = self._programs[key]
         sets = self.octaves if self.octave_mode == "new_features" else 1
         n = self.n_points[(octave % sets) % len(self.n_points)]  # the feature set this octave reads
-        if top >= n:
-            raise IndexError(f"index {top} is out of bounds for dimension 5 with size {n}")
-        return dterms, rterms
+        if top >= n or low < -n:
+            raise IndexError(f"index {top if top >= n else low} is out of bounds for dimension 5 with size {n}")
+        if n not in resolved:
+            resolved[n] = self._resolve(rterms, n, key[1])
+        return dterms, resolved[n]
 
     # ---- state (py/noise_generation.py:1362-1447)
     def voronoi_reset(self, *args):
@@ -1390,8 +1441,9 @@ class VoronoiNoiseGenerator(NoiseGenerator):
                 raw = hip_lib.voronoi_program(dterms, [{"op": "cellid_raw", "fns": r["fns"]}])
                 ids = hip_lib.voronoi_octave_(torch.zeros_like(out), fp, raw, scale=scale, z_norm=z_norm, amplitude=1.0, fuzz=fuzz)
                 aux[t:t + 1].copy_(hip_lib.minmax_rows(ids, 1, ids.numel())[1])
-        return hip_lib.voronoi_octave_(out, fp, hip_lib.voronoi_program(dterms, rterms), scale=scale, z_norm=z_norm, amplitude=amplitude, aux=aux,
-                                       final_div=final_div, fuzz=fuzz)
+        octave_ = hip_lib.voronoi_rank_octave_ if any(self._past_f4(r) for r in rterms) else hip_lib.voronoi_octave_  # the program as a whole
+        return octave_(out, fp, hip_lib.voronoi_program(dterms, rterms), scale=scale, z_norm=z_norm, amplitude=amplitude, aux=aux,
+                       final_div=final_div, fuzz=fuzz)
 
     def _plane_octave(self, fp: Tensor, dterms, rterms, scale: float, z_norm: float, fuzz=None) -> Tensor:
         """An octave with plane modes, summed term by term in the reference's order: the leading pointwise terms in one launch (their sum

@@ -510,6 +510,8 @@ int sonar_collatz_mix_f32(float* acc, const float* out1, const float* second, in
 #define SONAR_VORONOI_R_SOFTMIN 4
 #define SONAR_VORONOI_R_CELLID 5
 #define SONAR_VORONOI_R_CELLID_RAW 6
+#define SONAR_VORONOI_R_SOFTMIN_SORTED 7 /* sonar_voronoi_rank_octave_f32 only */
+#define SONAR_VORONOI_RANK_ROW_N 256     /* the longest row SOFTMIN_SORTED is built for: 64 lanes' rows and the staged points in LDS */
 typedef struct sonar_voronoi_dterm {
     int32_t metric, idx, n_xform;
     int32_t xform[SONAR_VORONOI_MAX_CHAIN];
@@ -550,6 +552,23 @@ int sonar_voronoi_octave_f32(const float* fp, float* out, const float* aux, int6
 int sonar_voronoi_fuzz_octave_f32(const float* fp, float* out, const float* aux, const float* u, uint32_t* stats, int64_t B, int64_t C,
                                   int64_t H, int64_t W, int64_t N, float scale, float z_norm, float amplitude, float final_div, int flags,
                                   const sonar_voronoi_program* prog, int pass, int fuzz_term, double fuzz, uint64_t seed, uint64_t stream_id,
+                                  int64_t elem_offset, void* stream);
+
+/* The rank route: the same octave with idx1 / idx2 anywhere in [0, N) -- `f:idx=k` past f4, the median (the host passes rank
+ * (N - 1) / 2, torch.median's lower middle) -- and SOFTMIN_SORTED (softmin:use_sorted: the weight of point j multiplies the j-th smallest
+ * value).  The k-th smallest value of a pixel's row is found exactly, bit by bit on the floats' ordered-integer image: 32 sweeps over the
+ * points that count, for both ranks of every term at once, the values below the candidate; one more sweep in front serves SOFTMIN,
+ * SOFTMIN_SORTED and the CELLID ops.  With ranks inside 0..3 the output has sonar_voronoi_octave_f32's bits.  SOFTMIN_SORTED runs in
+ * workgroups of one wave that hold each pixel's row in LDS (N <= SONAR_VORONOI_RANK_ROW_N) and ranks every value in it.
+ * fuzz_term -1: no fuzz distance term (u and stats NULL); else the arguments of sonar_voronoi_fuzz_octave_f32's pass 2, after its passes
+ * 0 and 1 have filled `stats`.
+ * Every term is a value here: the write-through of the reference's bare `f` views into the sorted row their sum shares is restated by
+ * sonar_voronoi_octave_f32 alone, and the host keeps such sums there (the median is no view).
+ * SONAR_ERR_ARG beyond the entry points' above: a rank below 0 or not below N, u or stats without a fuzz term.  SONAR_ERR_UNSUPPORTED:
+ * SOFTMIN_SORTED with N > SONAR_VORONOI_RANK_ROW_N. */
+int sonar_voronoi_rank_octave_f32(const float* fp, float* out, const float* aux, const float* u, uint32_t* stats, int64_t B, int64_t C,
+                                  int64_t H, int64_t W, int64_t N, float scale, float z_norm, float amplitude, float final_div, int flags,
+                                  const sonar_voronoi_program* prog, int fuzz_term, double fuzz, uint64_t seed, uint64_t stream_id,
                                   int64_t elem_offset, void* stream);
 
 /* The result modes that work on whole planes of inner results (each inner term one sonar_voronoi_octave_f32 launch into a temporary):
