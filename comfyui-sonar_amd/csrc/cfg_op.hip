@@ -2,14 +2,12 @@
 //   prepare: f(t) = (x - t) / sigma[sample] (prediction flip) or t;  t2_out = f(t2);  result = f(t1) - f(t2)   (or f(t1) without t2)
 //   finish:  r = result + t2;  flip: r = x - sigma[sample] * r;  out = blend(t1_orig, r, w)  (or r), written once in t1_orig's dtype
 // Between the two everything is fp32; x / t1 / t2 / t1_orig arrive in fp32, fp16 or bf16 and are widened at load.  Both are HBM-bound (with
-// flip and t2: 3 reads + 2 writes, and 4 reads + 1 write): the shape of elementwise.hip -- one 4-element item per thread (16 bytes of fp32,
-// 8 of a half type), grid-stride, scalar tail, and the scalar route for buffers that are not 16-byte aligned.  Every operation is rounded
+// flip and t2: 3 reads + 2 writes, and 4 reads + 1 write): the shape of ew_driver.h's ew_kernel -- one 4-element item per thread (16 bytes
+// of fp32, 8 of a half type), grid-stride, scalar tail, and the scalar route for buffers that are not 16-byte aligned.  Every operation is rounded
 // on its own (-ffp-contract=off) in the reference's order, the division is a true division: on fp32 inputs the bits are the reference's.
 #include <math.h>
 
-#include <algorithm>
-
-#include "common.h"
+#include "ew_driver.h"
 
 namespace sonar {
 
@@ -160,35 +158,13 @@ struct CfgFinishOp {
     }
 };
 
-// elementwise.hip's driver: op.run<V>(first element) per item, grid-stride; block 0 takes the n % V tail one element at a time
-template <int V, typename Op>
-__global__ void __launch_bounds__(kBlock) cfg_op_kernel(Op op, int64_t n) {
-    kernarg_touch_for(op, n);
-    const int64_t nv = n / V;
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < nv; i += stride) op.template run<V>(i * V);
-    if constexpr (V > 1) {
-        if (blockIdx.x == 0)
-            for (int64_t i = nv * V + threadIdx.x; i < n; i += kBlock) op.template run<1>(i);
-    }
-}
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }  // null counts as aligned
-static inline int grid_items(int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>((items + kBlock - 1) / kBlock, 1 << 20)); }
-
-template <typename Op>
-static int launch_cfg_op(Op op, int64_t n, bool vec_ok, hipStream_t st, const char* what) {
-    if (vec_ok) hipLaunchKernelGGL((cfg_op_kernel<4, Op>), dim3(grid_items(n / 4 + 1)), dim3(kBlock), 0, st, op, n);
-    else hipLaunchKernelGGL((cfg_op_kernel<1, Op>), dim3(grid_items(n)), dim3(kBlock), 0, st, op, n);
-    return check_launch(what);
-}
-
+// Both ops run on ew_driver.h's driver (ew_kernel through launch_ew); a null pointer counts as aligned.
 template <typename T>
 static int prepare_typed(const void* x, const void* t1, const void* t2, const float* sigma, int per_sample, float* result, float* t2_out,
                          int64_t n, int64_t inner, hipStream_t st) {
     CfgPrepareOp<T> op{(const T*)x, (const T*)t1, (const T*)t2, sigma, result, t2_out, inner, per_sample};
     const bool vec_ok = aligned16(x) && aligned16(t1) && aligned16(t2) && aligned16(result) && aligned16(t2_out);
-    return launch_cfg_op(op, n, vec_ok, st, "sonar_cfg_op_prepare");
+    return launch_ew(op, n, vec_ok, st, "sonar_cfg_op_prepare");
 }
 
 template <typename T>
@@ -196,7 +172,7 @@ static int finish_typed(const float* result, const float* t2, const void* x, con
                         int blend_mode, float w, void* out, int64_t n, int64_t inner, hipStream_t st) {
     CfgFinishOp<T> op{result, t2, (const T*)x, sigma, (const T*)t1_orig, (T*)out, inner, per_sample, blend_mode, w};
     const bool vec_ok = aligned16(result) && aligned16(t2) && aligned16(x) && aligned16(t1_orig) && aligned16(out);
-    return launch_cfg_op(op, n, vec_ok, st, "sonar_cfg_op_finish");
+    return launch_ew(op, n, vec_ok, st, "sonar_cfg_op_finish");
 }
 
 // n, inner and sigma_n against each other (sigma_n is looked at only with a sigma)

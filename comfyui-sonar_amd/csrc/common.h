@@ -408,7 +408,7 @@ __device__ __forceinline__ T blend(int mode, T a, T b, T t) {
     return a - b * t;
 }
 
-// ---- per-row / per-group updates (elementwise.hip's row kernels and group_stats.hip's strided ones share the arithmetic) ------------
+// ---- per-row / per-group updates (rows.hip's row kernels and group_stats.hip's strided ones share the arithmetic) ------------
 // sonar_row_affine_f32: op 0 (x - a) / b, op 1 x * b + a
 __device__ __forceinline__ float row_affine_value(int op, float x, float a, float b) { return op == 0 ? (x - a) / b : x * b + a; }
 

@@ -16,7 +16,7 @@
 // members are cut into S slices (split_of below), every (group, slice) leaves its partial results in the workspace and a second launch
 // adds them in slice order: a function of the shape alone, so two runs give the same bits (no atomics).
 //
-// Accumulation: rowstats_kernel's (elementwise.hip) -- sum and sum of squares in fp64 (a product of two floats is exact in a double), mean
+// Accumulation: rowstats_kernel's (rows.hip) -- sum and sum of squares in fp64 (a product of two floats is exact in a double), mean
 // = s / n, var = (q - s * mean) / (n - 1), the same last lines (finish_mean_std) -- with the partial sums of lanes, waves and slices added
 // in fp64 in a fixed order.  n == 1 gives 0 / 0 = NaN like torch.  Min / max are fminf / fmaxf folds as in minmax_rows_kernel.
 //
@@ -281,7 +281,7 @@ __global__ void __launch_bounds__(kBlock) group_div_kernel(float* x, Segs sg, ui
         x[i] = x[i] / d[group_of(sg, (uint32_t)i)];
 }
 
-// scale_rows_kernel's last pass (elementwise.hip; py/utils.py:97-99) with the (std, mean of x / std) of the element's group
+// scale_rows_kernel's last pass (rows.hip; py/utils.py:97-99) with the (std, mean of x / std) of the element's group
 __global__ void __launch_bounds__(kBlock) group_scale_noise_kernel(float* x, Segs sg, uint32_t total, const float* __restrict__ sd,
                                                                     const float* __restrict__ mean, float factor) {
     kernarg_touch_for(x, sg, total, sd, mean, factor);

@@ -30,7 +30,7 @@ struct ComposeArgs {
     float tmin, tmax, span, eps, multiplier, strength;
 };
 
-// normalize_to_scale's value sequence (the same as minmax_rescale_kernel, elementwise.hip), then `result *= noise_multiplier`
+// normalize_to_scale's value sequence (the same as minmax_rescale_kernel, rows.hip), then `result *= noise_multiplier`
 __device__ __forceinline__ float prepare_noise(float n, bool normalize, float lo, float denom, const ComposeArgs& a) {
     if (normalize) {
         float v = __fsub_rn(n, lo) / denom;

@@ -19,7 +19,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "ew_driver.h"  // aligned16
 
 namespace sonar {
 namespace {
@@ -331,8 +331,6 @@ __global__ void __launch_bounds__(kBlock) noise_params_apply_kernel(const TS* __
         }
     }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // tiles of `extent` values per plane at vector width v; false: more tiles than a 32-bit unit index holds
 inline bool tiling(int64_t planes, int64_t extent, int v, uint32_t& chunks, uint32_t& units) {

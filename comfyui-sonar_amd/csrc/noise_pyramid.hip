@@ -319,7 +319,7 @@ __device__ __forceinline__ NormDecision decide_norm_as(const double* __restrict_
     return *sh;
 }
 // scale_noise_kernel's value sequence -- subtract, IEEE quotient, multiply -- with the quotient by the correctly rounded reciprocal and one
-// residual step (elementwise.hip, PendingNorm: the same bits as `v / std` for every v in the normal range)
+// residual step (sampler_steps.hip, PendingNorm:the same bits as `v / std` for every v in the normal range)
 struct ExactNorm {
     float mean, stdv, inv_std, factor;
     bool sub, div, mul;

@@ -5,11 +5,9 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "ew_driver.h"  // aligned16
 
 namespace sonar {
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 #ifdef SONAR_NG_TRACE  // profiling builds: cycle stamps of thread 0 of the first 256 workgroups at the phase boundaries (scratch/ng_trace.py)
 extern __device__ unsigned long long g_ng_trace[256 * 16];  // defined in noise_pyramid.hip, the one unit that stamps

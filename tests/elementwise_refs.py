@@ -1,5 +1,5 @@
-"""Shared by tests/test_elementwise_refs_cpu.py and tests/test_gpu_elementwise.py: plain torch restatements of the operations of
-csrc/elementwise.hip that the step kernels and the noise-type helpers implement, the seeded inputs the GPU tests feed them, and the
+"""Shared by tests/test_elementwise_refs_cpu.py and tests/test_gpu_elementwise.py: plain torch restatements of the operations that
+the step kernels (csrc/sampler_steps.hip) and the noise-type helpers (csrc/elementwise.hip, rows.hip, spectral_ops.hip) implement, the seeded inputs the GPU tests feed them, and the
 comparison helpers.
 
 Every restatement is dtype-generic: it computes in the dtype of its tensor arguments.  The GPU tests hand it float64 copies of the

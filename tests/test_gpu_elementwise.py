@@ -1,6 +1,7 @@
-"""Kernel-level parity (-m gpu) of csrc/elementwise.hip's sampler-step kernels and of the helper entry points the noise types are built
-from: every case is called through hip_lib and compared with a float64 reference (tests/elementwise_refs.py, itself pinned by
-tests/test_elementwise_refs_cpu.py) of the float32 inputs the kernel received, rounded once.
+"""Kernel-level parity (-m gpu) of the sampler-step kernels (csrc/sampler_steps.hip) and of the helper entry points the noise types are
+built from (csrc/elementwise.hip, csrc/rows.hip, csrc/spectral_ops.hip): every case is called through hip_lib and compared with a
+float64 reference (tests/elementwise_refs.py, itself pinned by tests/test_elementwise_refs_cpu.py) of the float32 inputs the kernel
+received, rounded once.
 
 Tolerances
   exact (torch.equal)   : where a kernel only selects or copies -- amax_mid, NaN / zero placement, the skipped sign of signed_rescale,
@@ -12,7 +13,7 @@ Tolerances
 No element is dropped or masked except where the reference itself is NaN (positions placed in advance, compared in kind, below 1 % of
 the test's elements: R.within asserts all three).
 
-Left out: grid_stream's cap at 2^20 blocks (csrc/elementwise.hip) takes 2^30 elements to reach -- four 4 GiB operands for a step kernel.
+Left out: grid_stream's cap at 2^20 blocks (csrc/ew_driver.h) takes 2^30 elements to reach -- four 4 GiB operands for a step kernel.
 """
 import pytest
 import torch

@@ -1,7 +1,7 @@
 """Kernel-level parity (-m gpu): the statistics / scale_noise, blend, generator, resampling and power-noise entry points of
 libsonar_hip.so and one aligned shape of sonar_momentum_euler_f32, called through ctypes on a real MI355X, against the CPU oracle
-(oracle/sonar_oracle.py) on the committed golden vectors and on seeded inputs.  The sampler-step kernels and the helper entry points
-of csrc/elementwise.hip (layouts, history outputs, reductions over a middle axis, rescales, spectral helpers) are pinned to float64
+(oracle/sonar_oracle.py) on the committed golden vectors and on seeded inputs.  The sampler-step kernels (csrc/sampler_steps.hip) and the helper entry points
+of csrc/elementwise.hip, rows.hip and spectral_ops.hip (layouts, history outputs, reductions over a middle axis, rescales, spectral helpers) are pinned to float64
 references in tests/test_gpu_elementwise.py; the wavelet, quantile, distro, image and latent-op kernels in their own test_gpu_* files.
 
 Tolerance (fp32 path, stated per north_star "within a stated fp32 tolerance"):
