@@ -1709,9 +1709,13 @@ def axis_taps(x: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor, axis: int,
     kind = _wavelet_dtype(x)
     if axis not in (-1, -2) or x.ndim < 2 or not x.is_contiguous() or coef.dtype != x.dtype or idx.dtype != torch.int32:
         raise SonarHipError("axis_taps: a contiguous tensor, axis -1 / -2 and tables of matching type are required")
+    if idx.ndim != 2 or idx.shape != coef.shape:  # the kernel reads taps entries per output row from both tables
+        raise SonarHipError(f"axis_taps: idx and coef must be 2-D [n_out, taps] tables of one shape (got {tuple(idx.shape)} and {tuple(coef.shape)})")
     n_out, taps = idx.shape
     n_in = x.shape[axis]
     inner = x.shape[-1] if axis == -2 else 1
+    if n_in * inner == 0:
+        raise SonarHipError(f"axis_taps: nothing to read along axis {axis} of {tuple(x.shape)}")
     outer = x.numel() // (n_in * inner)
     shape = list(x.shape)
     shape[axis] = n_out
@@ -1720,7 +1724,7 @@ def axis_taps(x: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor, axis: int,
     elif list(out.shape) != shape or not out.is_contiguous() or out.dtype != x.dtype:
         raise SonarHipError("axis_taps: output shape mismatch")
     fn = load().sonar_axis_taps_f32 if kind == "f32" else load().sonar_axis_taps_f64
-    _check(fn(_dev(x, "x", x.dtype), _dev(out, "out", x.dtype), outer, n_in, n_out, inner, idx.data_ptr(), _dev(coef, "coef", x.dtype), taps,
+    _check(fn(_dev(x, "x", x.dtype), _dev(out, "out", x.dtype), outer, n_in, n_out, inner, _dev(idx, "idx", torch.int32), _dev(coef, "coef", x.dtype), taps,
               int(bool(accumulate)), _stream()), f"sonar_axis_taps_{kind}")
     return out
 
@@ -1728,7 +1732,11 @@ def axis_taps(x: torch.Tensor, idx: torch.Tensor, coef: torch.Tensor, axis: int,
 def dtcwt_q2c(lh: torch.Tensor, hh: torch.Tensor, hl: torch.Tensor) -> torch.Tensor:
     """Three [B, C, 2h, 2w] planes -> [B, C, 6, h, w, 2] complex bands (orientation order 15 .. 165 degrees)."""
     kind = _wavelet_dtype(lh)
+    if lh.ndim != 4 or hh.shape != lh.shape or hl.shape != lh.shape:  # the kernel takes every plane's extent from lh
+        raise SonarHipError(f"dtcwt_q2c: three [B, C, 2h, 2w] planes of one shape are required (got {tuple(lh.shape)}, {tuple(hh.shape)}, {tuple(hl.shape)})")
     B, Cc, H2, W2 = lh.shape
+    if H2 % 2 or W2 % 2:
+        raise SonarHipError(f"dtcwt_q2c: the planes are read in 2 x 2 quads; {H2} x {W2} has an odd side")
     out = torch.empty((B, Cc, 6, H2 // 2, W2 // 2, 2), dtype=lh.dtype, device=lh.device)
     fn = load().sonar_dtcwt_q2c_f32 if kind == "f32" else load().sonar_dtcwt_q2c_f64
     _check(fn(_dev(lh, "lh", lh.dtype), _dev(hh, "hh", lh.dtype), _dev(hl, "hl", lh.dtype), _dev(out, "bands", lh.dtype), B * Cc, H2 // 2, W2 // 2,
@@ -1739,9 +1747,9 @@ def dtcwt_q2c(lh: torch.Tensor, hh: torch.Tensor, hl: torch.Tensor) -> torch.Ten
 def dtcwt_c2q(bands: torch.Tensor):
     """[B, C, 6, h, w, 2] -> (lh, hh, hl), each [B, C, 2h, 2w]."""
     kind = _wavelet_dtype(bands)
-    B, Cc, six, h, w, two = bands.shape
-    if six != 6 or two != 2:
+    if bands.ndim != 6 or bands.shape[2] != 6 or bands.shape[5] != 2:
         raise SonarHipError("dtcwt_c2q: bands must be [B, C, 6, h, w, 2]")
+    B, Cc, _six, h, w, _two = bands.shape
     bands = bands.contiguous()
     outs = [torch.empty((B, Cc, 2 * h, 2 * w), dtype=bands.dtype, device=bands.device) for _ in range(3)]
     fn = load().sonar_dtcwt_c2q_f32 if kind == "f32" else load().sonar_dtcwt_c2q_f64

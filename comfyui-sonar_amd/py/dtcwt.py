@@ -189,10 +189,10 @@ class DTCWT:
 
     def inverse(self, coeffs) -> torch.Tensor:
         yl, yh = coeffs
+        if any(h is None or h.numel() == 0 for h in yh):  # before the first launch: a coarser level reads the shape of the finer one
+            raise hip_lib.SonarHipError("DTCWT.inverse: every level's bands are required")
         ll = yl.contiguous()
         for j in range(len(yh) - 1, -1, -1):
-            if yh[j] is None or yh[j].numel() == 0:
-                raise hip_lib.SonarHipError("DTCWT.inverse: every level's bands are required")
             lh, hh, hl = hip_lib.dtcwt_c2q(yh[j])
             if tuple(ll.shape[-2:]) != tuple(lh.shape[-2:]):
                 raise hip_lib.SonarHipError(f"DTCWT.inverse: level {j + 1} low-pass {tuple(ll.shape[-2:])} does not match its bands {tuple(lh.shape[-2:])}")
