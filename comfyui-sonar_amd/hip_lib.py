@@ -120,6 +120,8 @@ SIGNATURES = {
     "sonar_perlin_generate_acc_f32": (_I, [_P, _P, _I64, _I64, _I64, _F, _U64, _U64, _I64, _P]),
     "sonar_brownian_bridge_f32": (_I, [_P, _P, _P, _F, _P, _F, _P, _F, _I64, _I64, _P, _P, _I, _U64, _P, _I64, _P, _P]),
     "sonar_brownian_point_f32": (_I, [_P, _P, _P, _F, _I64, _I64, _P, _P, _I, _U64, _P, _I64, _P]),
+    "sonar_brownian_pair_f32": (_I, [_P, _P, _P, _P, _P, _F, _F, _P, _F, _P, _F, _P, _F, _P, _F, _I64, _I64, _P, _P, _I, _P, _P, _I, _P, _P, _I,
+                                     _U64, _P, _I64, _P, _P, _P]),
     "sonar_perlin_terms_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _P]),
     "sonar_perlin_lattice_f32": (_I, [_P, _I64, _I64, _I64, _I64, _I, _U64, _U64, _P]),
     "sonar_perlin_apply_f32": (_I, [_P, _P, _P, _I64, _I64, _I64, _F, _P, _P]),
@@ -1021,6 +1023,34 @@ def brownian_bridge(shape, device, node_ids, coefs, seed: int, elem_offset: int 
             return out, w
         node_ids, coefs = node_ids[BROWNIAN_MAX_TERMS:], coefs[BROWNIAN_MAX_TERMS:]
         base_a, fa, base_b, fb = w, 1.0, None, 0.0
+
+
+BROWNIAN_LONG_TERMS = 4  # kBrownLongTerms (csrc/noise_brownian.hip): expansions from this length on run in the larger workgroup
+
+
+def brownian_pair(shape, device, shared, only_1, only_2, seed: int, elem_offset: int = 0, latent_seeds: Optional[torch.Tensor] = None, *,
+                  base_1=(None, 0.0, None, 0.0), base_2=(None, 0.0, None, 0.0), prev: Optional[torch.Tensor] = None, scale_1: float = 1.0,
+                  scale_2: float = 1.0, want_w: bool = True, w_out=None, partials=(None, None)):
+    """Two points of one path from one launch (``sonar_brownian_pair_f32``): W_i = fa_i * base_a_i + fb_i * base_b_i + the point's terms,
+    each term list a pair (ascending node ids, coefficients) -- ``shared`` counts for both points with one coefficient, ``only_i`` for
+    point i.  ``base_i`` = (base_a, fa, base_b, fb).  Returns ((scale_1 * (W_1 - prev), W_1 or None), (scale_2 * (W_2 - prev), W_2 or
+    None)), bit for bit what two ``brownian_bridge`` calls return; ``partials`` = the two increments' statistics workspaces, ``w_out`` = two
+    tensors to receive W_1, W_2 instead of fresh ones."""
+    outs = [torch.empty(tuple(shape), dtype=torch.float32, device=device) for _ in range(2)]
+    ws = list(w_out) if w_out is not None else [torch.empty(tuple(shape), dtype=torch.float32, device=device) if want_w else None for _ in range(2)]
+    n = math.prod(shape)
+    lists = []
+    for ids, cf in (shared, only_1, only_2):
+        lists += [(C.c_uint64 * len(ids))(*[int(v) & (2**64 - 1) for v in ids]), (C.c_float * len(cf))(*[float(v) for v in cf]), len(ids)]
+    bases = []
+    for a, fa, b, fb in (base_1, base_2):
+        bases += [_opt(a, "base_a"), float(fa), _opt(b, "base_b"), float(fb)]
+    _check(load().sonar_brownian_pair_f32(_dev(outs[0], "out_1"), _dev(outs[1], "out_2"), _opt(ws[0], "w_out_1"), _opt(ws[1], "w_out_2"),
+                                          _opt(prev, "prev"), float(scale_1), float(scale_2), *bases, n, elem_offset, *lists, seed & (2**64 - 1),
+                                          None if latent_seeds is None else latent_seeds.data_ptr(), n // shape[0],
+                                          _opt(partials[0], "partials_1", torch.float64), _opt(partials[1], "partials_2", torch.float64), _stream()),
+           "sonar_brownian_pair_f32")
+    return (outs[0], ws[0]), (outs[1], ws[1])
 
 
 def perlin_terms(angles: torch.Tensor, blend_mode: str = "lerp") -> torch.Tensor:

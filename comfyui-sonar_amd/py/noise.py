@@ -133,6 +133,18 @@ def _for_latent_dtype(x: Tensor, build: Callable) -> Callable:
         utils.pop_stats(out)
         return out.to(dtype)
 
+    both = getattr(inner, "deferred_pair", None)
+    if both is not None:
+        def deferred_pair(sigma, sigma_mid, sigma_next, defer=True):
+            """The inner sampler's two-point query, each draw finished and rounded as a call's is."""
+            made = both(sigma, sigma_mid, sigma_next, defer=False)
+            if made is None:
+                return None
+            for out, _ in made:
+                utils.pop_stats(out)
+            return tuple((out.to(dtype), None) for out, _ in made)
+
+        noise_sampler.deferred_pair = deferred_pair
     return noise_sampler
 
 
@@ -237,18 +249,22 @@ class CustomNoiseChain:
                 total = first[0] if first[1] == 1.0 else scale_noise(first[0], first[1], normalized=False)
             return total, False
 
-        def noise_sampler(sigma, sigma_next):
-            total, final = summed(sigma, sigma_next)
+        def finished(total, final):
             if final or (not normalized and factor == 1):
                 return total  # nothing left to do; a statistics tag of the sum (if any) stays valid for a normalising layer above
             return scale_noise(total, factor, normalized=normalized)
+
+        def noise_sampler(sigma, sigma_next):
+            return finished(*summed(sigma, sigma_next))
 
         def deferred(sigma, sigma_next):
             """(tensor, norm) for a consumer that can apply the final normalisation while it reads the noise (the Sonar sampler steps,
             ``noise_norm`` of sonar_momentum_euler_f32 / sonar_dpmpp_stage*_f32): the sum with its statistics already reduced comes
             back as it is and ``norm`` holds the decision on the device (``hip_lib.norm_decision``) -- the read + write of
             ``scale_noise`` is saved.  ``norm`` None: the tensor is final (every other case)."""
-            total, final = summed(sigma, sigma_next)
+            return pending(*summed(sigma, sigma_next))
+
+        def pending(total, final):
             if final or (not normalized and factor == 1):
                 return total, None
             partials = utils.pop_stats(total) if normalized else None
@@ -258,6 +274,18 @@ class CustomNoiseChain:
                 return scale_noise(total, factor, normalized=normalized), None
             return total, hip_lib.norm_decision(partials, total.numel(), factor)
 
+        both = getattr(samplers[0], "deferred_pair", None) if len(samplers) == 1 else None
+        if both is not None:
+            def deferred_pair(sigma, sigma_mid, sigma_next, defer=True):
+                """A chain of ONE item that answers a two-point query (Brownian noise): (``deferred(sigma, sigma_mid)``,
+                ``deferred(sigma, sigma_next)``) -- with ``defer`` False the two finished tensors, ``norm`` None -- from one launch.  The item's
+                draw is what ``summed`` makes of it (its factor applied, its statistics tag kept); a longer chain keeps two calls."""
+                made = both(sigma, sigma_mid, sigma_next)
+                if made is None:
+                    return None
+                return tuple(pending(total, False) if defer else (finished(total, False), None) for total, _ in made)
+
+            noise_sampler.deferred_pair = deferred_pair
         if all(getattr(ns, "plan_static", False) for ns in samplers):
             # every item draws on the device from nothing but the RNG position: the step is traced once and then issued by one foreign
             # call (hip_lib.Planned: the same entry points with the same arguments, the same bits)
@@ -388,6 +416,28 @@ class NoiseSampler:
                 noise, partials = got
                 return noise, hip_lib.norm_decision(partials, noise.numel(), self.factor)
         return self(*args), None
+
+    @property
+    def deferred_pair(self):
+        """None unless the generator answers a two-point query (a bare Brownian generator: ``pair``); then the callable
+        (sigma, sigma_mid, sigma_next) -> (``deferred(sigma, sigma_mid)``, ``deferred(sigma, sigma_next)``) with both draws from that query
+        -- one launch instead of two, the same tensors (``defer`` is accepted for the chain's protocol: the tensors are always final)."""
+        draw = getattr(self.noise_sampler, "pair", None)
+        if draw is None:
+            return None
+
+        def both(sigma, sigma_mid, sigma_next, defer=True):
+            gen = self.noise_sampler
+            gen.pre_hook()
+            made = []
+            for noise in draw(*(self.transform(torch.as_tensor(s)) for s in (sigma, sigma_mid, sigma_next))):  # (_call, per draw)
+                noise = scale_noise(gen.output_hook(noise), self.factor, normalized=self.normalized)
+                if noise.dtype != self.dtype or noise.device != self.device:
+                    noise = noise.to(dtype=self.dtype, device=self.device)
+                made.append((noise, None))
+            return tuple(made)
+
+        return both
 
     def __call__(self, *args, **kwargs):
         if self._planned is not None and not kwargs and len(args) == 2:

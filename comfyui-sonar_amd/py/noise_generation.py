@@ -2027,6 +2027,20 @@ class BrownianPath:
             stack.pop()
         return memo[t] if t in memo else base[t]
 
+    @staticmethod
+    def split_pair(c1: dict, c2: dict):
+        """Two points' expansions ({node id: coefficient}, as ``coefficients`` returns them) as the three term lists of a two-point query
+        (``sonar_brownian_pair_f32``): (shared, only_1, only_2), each (ascending node ids, coefficients).  THE RULE: a node is shared
+        when both points hold it with the SAME fp64 coefficient; a common node whose coefficient differs goes on both private lists, each
+        with its own (the kernel still draws its normals once).  No per-point gain is involved, so point i's expansion is exactly shared +
+        only_i and the three lists together are never longer than the two expansions.  Inside the tree nearly every common ancestor ends
+        up on both private lists (its coefficient is its hat function at the point's time); shared nodes are what two extension points
+        beyond the range have in common."""
+        shared = sorted(k for k in c1.keys() & c2.keys() if c1[k] == c2[k])
+        taken = set(shared)
+        only_1, only_2 = (sorted(k for k in c if k not in taken) for c in (c1, c2))
+        return (shared, [c1[k] for k in shared]), (only_1, [c1[k] for k in only_1]), (only_2, [c2[k] for k in only_2])
+
     def increment(self, t0: float, t1: float):
         """(node ids, coefficients) of (W(t_max) - W(t_min)) / sqrt(t_max - t_min); the smaller time is defined first."""
         t0, t1 = self.resolve(t0), self.resolve(t1)
@@ -2161,23 +2175,36 @@ class BrownianTreeNoiseSampler:
 
     def _tree_point(self, t: float, *, prev, scale, want_out, fold, partials):
         """Tree mode's two-stage evaluation of a time inside the range (see TREE_COARSE_LEVEL); None: not applicable (a shallow tree)."""
+        ids, coefs, cell = self._tree_stage(t)
+        if cell is None:
+            return None
+        wa, fa, wb, fb = self._coarse_bases(*cell)
+        return self._emit(ids, coefs, base_a=wa, fa=fa, base_b=wb, fb=fb, prev=prev, scale=scale, want_out=want_out, fold=fold, partials=partials)
+
+    def _tree_stage(self, t: float):
+        """How a point of the tree is evaluated, on the host alone: (node ids, coefficients, cell) with cell = (ga, gb, fb) -- the two-stage
+        rule: the coarse cell's ends and t's place between them, the ids those below the coarse grid -- or None: the whole expansion
+        (a shallow tree, a time outside the range or on the coarse grid itself)."""
         path = self.path
         shift = path.tree_depth - self.TREE_COARSE_LEVEL
-        if shift < 2 or not path.t_lo < t < path.t_hi:
-            return None
-        g = path.grid_index(t)
-        ga = (g >> shift) << shift
-        terms = path.coefficients(t)
-        if g == ga:  # a point of the coarse grid itself: its expansion only holds top-level nodes
-            return None
-        gb = ga + (1 << shift)
-        ta, tb = path._grid_time(ga), path._grid_time(gb)
-        top = 1 << self.TREE_COARSE_LEVEL  # heap indices below it (and the root's id 0) belong to the coarse grid
-        ids = sorted(k for k in terms if k >= top)
-        wa, wb = self._coarse(ga), self._coarse(gb)
-        fb = (t - ta) / (tb - ta)
-        return self._emit(ids, [terms[k] for k in ids], base_a=wa, fa=1.0 - fb, base_b=wb, fb=fb, prev=prev, scale=scale, want_out=want_out, fold=fold,
-                          partials=partials)
+        terms = None
+        if shift >= 2 and path.t_lo < t < path.t_hi:
+            g = path.grid_index(t)
+            ga = (g >> shift) << shift
+            terms = path.coefficients(t)
+            if g != ga:  # (a point of the coarse grid itself: its expansion only holds top-level nodes)
+                gb = ga + (1 << shift)
+                ta, tb = path._grid_time(ga), path._grid_time(gb)
+                top = 1 << self.TREE_COARSE_LEVEL  # heap indices below it (and the root's id 0) belong to the coarse grid
+                ids = sorted(k for k in terms if k >= top)
+                return ids, [terms[k] for k in ids], (ga, gb, (t - ta) / (tb - ta))
+        terms = path.coefficients(t) if terms is None else terms
+        ids = sorted(terms)
+        return ids, [terms[k] for k in ids], None
+
+    def _coarse_bases(self, ga: int, gb: int, fb: float):
+        """(W(a), fa, W(b), fb) of a two-stage evaluation, the coarse tensors evaluated and kept when they are not."""
+        return self._coarse(ga), 1.0 - fb, self._coarse(gb), fb
 
     def _point(self, t: float, *, prev: Optional[Tensor] = None, scale: float = 1.0, want_out: bool = True, fold=None, partials=None):
         """(scale * (W(t) - prev) or None, W(t)) for a time that is not kept: the bridge between its two kept neighbours, else its expansion."""
@@ -2247,6 +2274,71 @@ class BrownianTreeNoiseSampler:
         out, _ = self._point(ta, prev=wb, scale=-scale, fold=fold, partials=partials)  # scale * (W(tb) - W(ta))
         return out
 
+    def _pair_targets(self, sigma, sigma_mid, sigma_next):
+        """``pair``'s one-launch case: (t, ((u_1, scale_1), (u_2, scale_2))) -- the common time and, per query, the other time with the
+        factor of W(u_i) - W(t) in ``self(sigma, .)`` -- or None where two calls are as cheap or the only way."""
+        path = self.path
+        if not path.tree_depth:
+            return None  # the path of bridges makes the second point FROM the first (its kept neighbour): two dependent launches
+        t0 = float(self.transform(torch.as_tensor(sigma)))
+        t = path.resolve(t0)
+        targets = []
+        for other in (sigma_mid, sigma_next):
+            t1 = float(self.transform(torch.as_tensor(other)))
+            u = path.resolve(t1)
+            if u == t or u in self._points:
+                return None  # no move (a zero increment or the increment's own expansion), or a kept point (a difference of two tensors)
+            if u == path.t_lo and t not in self._points:
+                return None  # W(t_lo) = 0 is not evaluated (nor kept) by a call that has W(t) to evaluate: out = scale * W(t)
+            # __call__: sign / sqrt(tb - ta) * (W(tb) - W(ta)) with ta < tb the two times in order
+            sign = self.sign * (1.0 if t0 <= t1 else -1.0)
+            targets.append((u, (sign if u > t else -sign) / math.sqrt(abs(u - t))))
+        if targets[0][0] == targets[1][0]:
+            return None  # the second query finds the first one's point kept
+        return t, tuple(targets)
+
+    def pair(self, sigma, sigma_mid, sigma_next, *, fold=None, partials=None):
+        """(self(sigma, sigma_mid), self(sigma, sigma_next)), observationally those two calls in that order -- the same bits, the same kept
+        points afterwards -- but where both have a path point to evaluate, ONE launch evaluates the two (``sonar_brownian_pair_f32``: nodes
+        the points have in common are drawn once, W(sigma) is read once).  ``partials``: a pair of statistics workspaces, one per increment."""
+        p1, p2 = partials if partials is not None else (None, None)
+        plan = self._pair_targets(sigma, sigma_mid, sigma_next) if fold is None else None
+        if plan is not None:
+            t, ((u1, scale_1), (u2, scale_2)) = plan
+            path = self.path
+            for u in (u1, u2):  # (__call__'s order: per query the smaller time first)
+                path.define(min(t, u))
+                path.define(max(t, u))
+            stages = [self._tree_stage(u) for u in (u1, u2)]  # (host arithmetic only: nothing is launched or kept before the decision)
+            shared, only_1, only_2 = path.split_pair(*(dict(zip(ids, coefs)) for ids, coefs, _ in stages))
+            long_1, long_2 = (len(ids) >= hip_lib.BROWNIAN_LONG_TERMS for ids, _, _ in stages)
+            # Statistics are reduced per block (a block owns a slot), so their bits depend on the launch that wrote the increment: both points
+            # must take the block size their own launches would (hip_lib.BROWNIAN_LONG_TERMS), and the first call's increment must come from
+            # u_1's launch -- with W(t) neither kept nor below u_1 (a run's first step) it comes from the launch that evaluates W(t)
+            same_stats = long_1 == long_2 and (t in self._points or t < u1)
+            if len(shared[0]) + len(only_1[0]) + len(only_2[0]) <= hip_lib.BROWNIAN_MAX_TERMS and (partials is None or same_stats):
+                prev = None if t == path.t_lo else self._cached(t)  # W(t_lo) = 0
+                if prev is None and t != path.t_lo:
+                    _, prev = self._point(t, want_out=False)  # (the first query would have evaluated and kept it as well)
+                ws = tuple(torch.empty(self.shape, dtype=torch.float32, device=self.device) for _ in range(2))
+                bases = []
+                for u, w, (_, _, cell) in zip((u1, u2), ws, stages):
+                    # the kept points move as the two calls move them: t looked up, the coarse ends fetched, the new point kept (its
+                    # tensor is filled by the launch below, which is queued before anything can read it)
+                    self._cached(t)
+                    bases.append((None, 0.0, None, 0.0) if cell is None else self._coarse_bases(*cell))
+                    self._remember(u, w)
+                try:
+                    (out_1, _), (out_2, _) = hip_lib.brownian_pair(self.shape, self.device, shared, only_1, only_2, self.seed, self.elem_offset,
+                                                                   self.latent_seeds, base_1=bases[0], base_2=bases[1], prev=prev,
+                                                                   scale_1=scale_1, scale_2=scale_2, w_out=ws, partials=(p1, p2))
+                except Exception:
+                    for u in (u1, u2):  # never filled
+                        self._points.pop(u, None)
+                    raise
+                return out_1, out_2
+        return self(sigma, sigma_mid, fold=fold, partials=p1), self(sigma, sigma_next, fold=fold, partials=p2)
+
 
 class BrownianNoiseGenerator(NoiseGenerator):
     """py/noise_generation.py:262-286."""
@@ -2268,6 +2360,11 @@ class BrownianNoiseGenerator(NoiseGenerator):
         # the increment's statistics come out of the same pass: the normalisation that usually follows (py/noise.py:245) needs no sweep
         partials = hip_lib.new_partials(self.device)
         return attach_stats(self.brownian_tree_ns(*args, partials=partials), partials)
+
+    def pair(self, sigma, sigma_mid, sigma_next):
+        """(generate(sigma, sigma_mid), generate(sigma, sigma_next)) from the sampler's two-point query: one launch where it can be."""
+        partials = tuple(hip_lib.new_partials(self.device) for _ in range(2))
+        return tuple(attach_stats(nz, p) for nz, p in zip(self.brownian_tree_ns.pair(sigma, sigma_mid, sigma_next, partials=partials), partials))
 
     accepts_prefix = True  # generate_into(..., pre=): the previous chain item's fold rides in this generator's kernel
 

@@ -149,12 +149,31 @@ class SonarBase:
         self.noise_sampler = noise_sampler
         return noise_sampler
 
-    def draw_noise(self, sigma, sigma_next, *, defer: bool = True):
+    brownian_pair = False  # (SonarDPMPPSDE: both Brownian increments of a step from one launch)
+    _noise_ahead = None    # (sigma_next object, (noise, norm)): a draw fetched along with the previous one (``then``)
+
+    def draw_noise(self, sigma, sigma_next, *, defer: bool = True, then=None):
         """(noise as fp32, norm): ``self.noise_sampler(sigma, sigma_next)``.  A sampler built by this package's noise chains can hand the
         sum back with its final normalisation still pending (``deferred``; ``norm`` = the decision on the device) for the step kernels to
-        apply while they read the noise; ``defer=False`` (or any other sampler) gives the finished tensor and ``norm`` None."""
+        apply while they read the noise; ``defer=False`` (or any other sampler) gives the finished tensor and ``norm`` None.
+        ``then``: the sigma of the draw that follows from the same ``sigma``.  A sampler that exposes ``deferred_pair`` (Brownian noise on
+        its own: the two path points come out of one launch) is asked for both draws, and the second is handed out when
+        ``draw_noise(sigma, then)`` asks for it -- the same tensors as the two draws give (``brownian_pair`` False: never)."""
+        ahead, self._noise_ahead = self._noise_ahead, None
+        if ahead is not None and ahead[0] is sigma_next and defer:
+            return ahead[1]
+        both = getattr(self.noise_sampler, "deferred_pair", None) if then is not None and defer and self.brownian_pair else None
+        got = both(sigma, sigma_next, then) if both is not None else None
+        if got is not None:
+            first, second = (self._finish_noise(nz, norm) for nz, norm in got)
+            self._noise_ahead = (then, second)
+            return first
         lazy = getattr(self.noise_sampler, "deferred", None) if defer else None
         nz, norm = lazy(sigma, sigma_next) if lazy is not None else (self.noise_sampler(sigma, sigma_next), None)
+        return self._finish_noise(nz, norm)
+
+    @staticmethod
+    def _finish_noise(nz, norm):
         if norm is not None and nz.dtype != torch.float32:
             nz, norm = hip_lib.apply_norm_(utils.as_f32(nz), norm), None
         nz = utils.as_f32(nz)
@@ -458,6 +477,10 @@ class SonarDPMPPSDE(SonarSampler):
     """py/sonar.py:626-820: DPM-Solver++(SDE), r = 1/2, with momentum on both half steps."""
 
     DEFAULT_NOISE_TYPE = noise.NoiseType.BROWNIAN
+    # True (on the class or an instance): a step's two Brownian increments (half step, full step) from ONE launch where the noise sampler
+    # can (``draw_noise``'s ``then``) -- the same tensors.  Off by default: on cfg5's shard the one launch measured slower than the two
+    # (565 against 465 us per step, profiles/brownian_pair_time.txt: two accumulator sets leave the kernel four waves per SIMD)
+    brownian_pair = False
 
     def __init__(self, eta: float = 1.0, s_noise: float = 1.0, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -490,7 +513,10 @@ class SonarDPMPPSDE(SonarSampler):
         # ---- stage 1
         kc = self.kernel_cfg(step_index)
         h_in = self._history_for_kernel(x, step_index, kc)
-        nz, norm = self.draw_noise(s_t, s_s)
+        # both increments are asked for from the same sigma: where the second one is fused into stage 2, a Brownian sampler makes it now
+        s_t_next = self.sigma_fn(t_next)
+        fuse_noise = not self.guidance_active(step_index)
+        nz, norm = self.draw_noise(s_t, s_s, then=s_t_next if fuse_noise else None)
         x32 = utils.as_f32(x)
         x_2, md1, hist = hip_lib.dpmpp_stage1(
             x32, utils.as_f32(denoised), h_in, kc, f32(sigma), f32((t - s_).expm1()), f32(self.sigma_fn(s_) / s_t), adjusted == 1,
@@ -499,11 +525,9 @@ class SonarDPMPPSDE(SonarSampler):
         self.history_d = hist
         denoised_2 = self.call_model(x_2, s_s)
         # ---- stage 2
-        s_t_next = self.sigma_fn(t_next)
         sd, su = get_ancestral_step(s_t, s_t_next, self.eta)
         t_down = self.t_fn(sd)
         kc2 = self.kernel_cfg(step_index)
-        fuse_noise = not self.guidance_active(step_index)
         nz2, norm2 = self.draw_noise(s_t, s_t_next) if fuse_noise else (None, None)
         x_out, dd, hist = hip_lib.dpmpp_stage2(
             x32, utils.as_f32(denoised_2), md1, self.history_d, kc2, f32(s_s), f32((t - t_down).expm1()),

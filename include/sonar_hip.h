@@ -721,6 +721,22 @@ int sonar_brownian_bridge_f32(float* out, float* w_out, const float* prev, float
                               const float* base_b, float fb, int64_t n, int64_t elem_offset, const uint64_t* node_ids,
                               const float* coefs, int nnodes, uint64_t seed, const uint64_t* latent_seeds, int64_t latent_elems,
                               double* partials /* nullable: (sum, sumsq) of `out`, SONAR_NPART pairs */, void* stream);
+/* Two points of the same path from one launch, both differenced against the same kept W (DPM++ SDE asks (t, s) and (t, t') per step):
+ *   W_i = fa_i * base_a_i + fb_i * base_b_i + sum over point i's nodes of coef * z(node, e),   out_i = scale_i * (W_i - prev),
+ * w_out_i = W_i (nullable).  Point i's nodes are the shared list (ONE coefficient, the same for both points) and its private list; a
+ * node may be on both private lists with a coefficient each.  Every list has strictly ascending 48-bit ids, the shared list is disjoint
+ * from the private ones.  z(node, .) is drawn once per node whichever points hold it, and each W_i is accumulated in ascending id order:
+ * out_i, w_out_i and partials_i are bit for bit what sonar_brownian_bridge_f32 gives for point i alone (same routes, same value
+ * families).  SONAR_ERR_ARG before any launch: a NULL output, two outputs sharing a buffer, an output aliasing a base or prev, n < 0 or
+ * n >= 2^31, an unsorted list.  SONAR_ERR_UNSUPPORTED (make two single-point queries): more than 96 terms over the three lists;
+ * statistics asked for while one expansion has fewer than 4 terms and the other has not (the single-point launches would differ in
+ * block size, and with it in the statistics' summation order). */
+int sonar_brownian_pair_f32(float* out_1, float* out_2, float* w_out_1, float* w_out_2, const float* prev, float scale_1, float scale_2,
+                            const float* base_a_1, float fa_1, const float* base_b_1, float fb_1, const float* base_a_2, float fa_2,
+                            const float* base_b_2, float fb_2, int64_t n, int64_t elem_offset, const uint64_t* shared_ids,
+                            const float* shared_coefs, int nshared, const uint64_t* ids_1, const float* coefs_1, int n_1,
+                            const uint64_t* ids_2, const float* coefs_2, int n_2, uint64_t seed, const uint64_t* latent_seeds,
+                            int64_t latent_elems, double* partials_1, double* partials_2, void* stream);
 
 /* Accumulating forms of the generators (noise chains: result = sum_i item_i * factor_i, py/noise.py:188-194).  Instead of writing
  * a fresh tensor that sonar_axpby_f32 then folds into the running sum (read 8N + write 4N more), the generator reads the sum and
