@@ -1,40 +1,14 @@
 // The streaming driver of the elementwise units (elementwise.hip, sampler_steps.hip, cfg_op.hip): an Op struct says what happens to V
-// consecutive elements, ew_kernel walks the tensor with it and launch_ew picks the 16 B/lane or the scalar route.  Also the one
-// definition of aligned16, which the generator units take from here through noise_stream.h.
+// consecutive elements (read and written through dtype_io.h's Pack / load / store), ew_kernel walks the tensor with it and launch_ew picks
+// the 4-element or the scalar route.  Also the one definition of aligned16, which the generator units take from here through noise_stream.h.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 
-#include "common.h"
+#include "dtype_io.h"  // Pack, load, store
 
 namespace sonar {
-
-// ------------------------------------------------------------------------------------------------
-// V-wide pack of floats (V = 4 -> one dwordx4 access per lane; V = 1 for unaligned buffers).
-template <int V>
-struct Pack {
-    float v[V];
-};
-template <int V>
-__device__ __forceinline__ Pack<V> load(const float* p, int64_t i) {
-    Pack<V> r;
-    if constexpr (V == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p + i);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-        r.v[0] = p[i];
-    }
-    return r;
-}
-template <int V, bool NT = false>  // (NT: the 16-byte stores with the non-temporal hint)
-__device__ __forceinline__ void store(float* p, int64_t i, const Pack<V>& r) {
-    if constexpr (V == 4) {
-        store4<NT>(p + i, r.v[0], r.v[1], r.v[2], r.v[3]);
-    } else {
-        p[i] = r.v[0];
-    }
-}
 
 // Generic driver: op.template run<V>(elem_index) handles V consecutive elements.
 template <int V, typename Op>

@@ -19,6 +19,7 @@
 
 #include <algorithm>
 
+#include "dtype_io.h"
 #include "ew_driver.h"  // aligned16
 
 namespace sonar {
@@ -36,66 +37,6 @@ __device__ __forceinline__ void unpack_ext(double w, float& mx, float& mn) {
     const uint64_t b = (uint64_t)__double_as_longlong(w);
     mx = __uint_as_float((uint32_t)(b >> 32));
     mn = __uint_as_float((uint32_t)b);
-}
-
-// 16-bit storage types (bit patterns; arithmetic is fp32), as in cfg_op.hip
-struct H16 {
-    uint16_t bits;
-};
-struct B16 {
-    uint16_t bits;
-};
-
-__device__ __forceinline__ float widen(float v) { return v; }
-__device__ __forceinline__ float widen(H16 v) { return (float)__builtin_bit_cast(_Float16, v.bits); }
-__device__ __forceinline__ float widen(B16 v) { return __uint_as_float((uint32_t)v.bits << 16); }
-
-template <typename T>
-__device__ __forceinline__ T narrow(float v);
-template <>
-__device__ __forceinline__ float narrow<float>(float v) { return v; }
-template <>
-__device__ __forceinline__ H16 narrow<H16>(float v) { return H16{__builtin_bit_cast(uint16_t, (_Float16)v)}; }  // nearest even
-template <>
-__device__ __forceinline__ B16 narrow<B16>(float v) {  // nearest even; NaN -> the quiet NaN torch writes
-    const uint32_t u = __float_as_uint(v);
-    if (v != v) return B16{0x7FC0};
-    return B16{(uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16)};
-}
-
-template <int V>
-struct Vals {
-    float v[V];
-};
-
-template <int V, typename T>
-__device__ __forceinline__ Vals<V> load_vals(const T* p, int64_t i) {
-    Vals<V> r;
-    if constexpr (V == 1) {
-        r.v[0] = widen(p[i]);
-    } else if constexpr (sizeof(T) == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p + i);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-        const uint2 t = *reinterpret_cast<const uint2*>(p + i);
-        r.v[0] = widen(T{(uint16_t)(t.x & 0xFFFFu)}); r.v[1] = widen(T{(uint16_t)(t.x >> 16)});
-        r.v[2] = widen(T{(uint16_t)(t.y & 0xFFFFu)}); r.v[3] = widen(T{(uint16_t)(t.y >> 16)});
-    }
-    return r;
-}
-
-template <int V, typename T>
-__device__ __forceinline__ void store_vals(T* p, int64_t i, const Vals<V>& r) {
-    if constexpr (V == 1) {
-        p[i] = narrow<T>(r.v[0]);
-    } else if constexpr (sizeof(T) == 4) {
-        *reinterpret_cast<float4*>(p + i) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    } else {
-        uint2 t;
-        t.x = (uint32_t)narrow<T>(r.v[0]).bits | ((uint32_t)narrow<T>(r.v[1]).bits << 16);
-        t.y = (uint32_t)narrow<T>(r.v[2]).bits | ((uint32_t)narrow<T>(r.v[3]).bits << 16);
-        *reinterpret_cast<uint2*>(p + i) = t;
-    }
 }
 
 __device__ __forceinline__ bool finite_f(float y) { return fabsf(y) < INFINITY; }  // false for NaN
@@ -182,7 +123,7 @@ __global__ void __launch_bounds__(kBlock) noise_params_scan_kernel(const T* __re
         const uint32_t p = u / chunks, c = u - p * chunks;
         const int64_t i = (int64_t)c * kTile + (int64_t)threadIdx.x * V;
         if (i < extent) {  // V == 4: both plane lengths are multiples of 4, the vector is inside, and wholly kept or wholly padding
-            const Vals<V> a = load_vals<V>(src, (int64_t)p * plane_in + i);
+            const Pack<V> a = load<V>(src, (int64_t)p * plane_in + i);
 #pragma unroll
             for (int k = 0; k < V; ++k) seen.add<FIX>(a.v[k], i < plane_out);
         }
@@ -194,7 +135,7 @@ __global__ void __launch_bounds__(kBlock) noise_params_scan_kernel(const T* __re
         const bool two = u + step < units && u + step > u;
         const bool w1 = two && whole(u + step, at1);
         if (w0 && w1) {  // two independent loads in flight
-            const Vals<V> a = load_vals<V>(src, at0), b = load_vals<V>(src, at1);
+            const Pack<V> a = load<V>(src, at0), b = load<V>(src, at1);
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 seen.add<FIX>(a.v[k], true);
@@ -203,7 +144,7 @@ __global__ void __launch_bounds__(kBlock) noise_params_scan_kernel(const T* __re
             continue;
         }
         if (w0) {
-            const Vals<V> a = load_vals<V>(src, at0);
+            const Pack<V> a = load<V>(src, at0);
 #pragma unroll
             for (int k = 0; k < V; ++k) seen.add<FIX>(a.v[k], true);
         } else {
@@ -211,7 +152,7 @@ __global__ void __launch_bounds__(kBlock) noise_params_scan_kernel(const T* __re
         }
         if (two) {
             if (w1) {
-                const Vals<V> b = load_vals<V>(src, at1);
+                const Pack<V> b = load<V>(src, at1);
 #pragma unroll
                 for (int k = 0; k < V; ++k) seen.add<FIX>(b.v[k], true);
             } else {
@@ -297,10 +238,10 @@ __global__ void __launch_bounds__(kBlock) noise_params_apply_kernel(const TS* __
         return ((int64_t)c + 1) * kTile <= plane_out;
     };
     auto one = [&](int64_t from, int64_t to) {
-        Vals<V> a = load_vals<V>(src, from);
+        Pack<V> a = load<V>(src, from);
 #pragma unroll
         for (int k = 0; k < V; ++k) a.v[k] = f(a.v[k]);
-        store_vals<V>(out, to, a);
+        store<V>(out, to, a);
     };
     auto guarded = [&](uint32_t u) {
         const uint32_t p = u / chunks, c = u - p * chunks;
@@ -313,14 +254,14 @@ __global__ void __launch_bounds__(kBlock) noise_params_apply_kernel(const TS* __
         const bool two = u + step < units && u + step > u;
         const bool w1 = two && place(u + step, f1, t1);
         if (w0 && w1) {
-            Vals<V> a = load_vals<V>(src, f0), b = load_vals<V>(src, f1);
+            Pack<V> a = load<V>(src, f0), b = load<V>(src, f1);
 #pragma unroll
             for (int k = 0; k < V; ++k) {
                 a.v[k] = f(a.v[k]);
                 b.v[k] = f(b.v[k]);
             }
-            store_vals<V>(out, t0, a);
-            store_vals<V>(out, t1, b);
+            store<V>(out, t0, a);
+            store<V>(out, t1, b);
             continue;
         }
         if (w0) one(f0, t0);
@@ -400,14 +341,6 @@ int apply_typed(const void* src, void* out, int64_t planes, int64_t plane_in, in
     return check_launch("sonar_noise_params_apply");
 }
 
-template <typename TS>
-int apply_src(int dst_dtype, const void* src, void* out, int64_t planes, int64_t plane_in, int64_t plane_out, int fix, int normalized, float factor,
-              float thr_sd, const double* partials, int npart, bool vec, hipStream_t st) {
-    if (dst_dtype == SONAR_DTYPE_F32) return apply_typed<TS, float>(src, out, planes, plane_in, plane_out, fix, normalized, factor, thr_sd, partials, npart, vec, st);
-    if (dst_dtype == SONAR_DTYPE_F16) return apply_typed<TS, H16>(src, out, planes, plane_in, plane_out, fix, normalized, factor, thr_sd, partials, npart, vec, st);
-    return apply_typed<TS, B16>(src, out, planes, plane_in, plane_out, fix, normalized, factor, thr_sd, partials, npart, vec, st);
-}
-
 }  // namespace
 }  // namespace sonar
 
@@ -417,7 +350,7 @@ extern "C" int64_t sonar_noise_params_ws_doubles(void) { return (int64_t)SONAR_N
 
 extern "C" int sonar_noise_params_scan(int src_dtype, const void* src, int64_t planes, int64_t plane_in, int64_t plane_out, int fix_invalid,
                                        double* partials, void* stream) {
-    SONAR_REQUIRE(src_dtype >= SONAR_DTYPE_F32 && src_dtype <= SONAR_DTYPE_BF16, SONAR_ERR_ARG, "sonar_noise_params_scan: unknown dtype %d", src_dtype);
+    SONAR_REQUIRE_DTYPE(src_dtype, "sonar_noise_params_scan");
     SONAR_REQUIRE(shape_ok(planes, plane_in, plane_out), SONAR_ERR_ARG, "sonar_noise_params_scan: bad planes / plane_in / plane_out");
     if (planes == 0) return SONAR_OK;
     SONAR_REQUIRE(src && partials, SONAR_ERR_ARG, "sonar_noise_params_scan: null pointer");
@@ -425,16 +358,16 @@ extern "C" int sonar_noise_params_scan(int src_dtype, const void* src, int64_t p
     ScanShape s;
     SONAR_REQUIRE(scan_shape(src, planes, plane_in, plane_out, fix_invalid != 0, s), SONAR_ERR_ARG, "sonar_noise_params_scan: too many tiles");
     const hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == SONAR_DTYPE_F32) return scan_typed<float>(src, plane_in, plane_out, fix_invalid != 0, s, partials, st);
-    if (src_dtype == SONAR_DTYPE_F16) return scan_typed<H16>(src, plane_in, plane_out, fix_invalid != 0, s, partials, st);
-    return scan_typed<B16>(src, plane_in, plane_out, fix_invalid != 0, s, partials, st);
+    return with_dtype(src_dtype, "sonar_noise_params_scan", [&](auto elem) {
+        return scan_typed<typename decltype(elem)::type>(src, plane_in, plane_out, fix_invalid != 0, s, partials, st);
+    });
 }
 
 extern "C" int sonar_noise_params_apply(int src_dtype, const void* src, int dst_dtype, void* out, int64_t planes, int64_t plane_in,
                                         int64_t plane_out, int fix_invalid, int normalized, float factor, float threshold_std_devs,
                                         const double* partials, void* stream) {
-    SONAR_REQUIRE(src_dtype >= SONAR_DTYPE_F32 && src_dtype <= SONAR_DTYPE_BF16 && dst_dtype >= SONAR_DTYPE_F32 && dst_dtype <= SONAR_DTYPE_BF16,
-                  SONAR_ERR_ARG, "sonar_noise_params_apply: unknown dtype %d / %d", src_dtype, dst_dtype);
+    SONAR_REQUIRE_DTYPE(src_dtype, "sonar_noise_params_apply");
+    SONAR_REQUIRE_DTYPE(dst_dtype, "sonar_noise_params_apply");
     SONAR_REQUIRE(shape_ok(planes, plane_in, plane_out), SONAR_ERR_ARG, "sonar_noise_params_apply: bad planes / plane_in / plane_out");
     const int fix = fix_invalid != 0, norm = normalized != 0;
     SONAR_REQUIRE(partials || !(fix || norm), SONAR_ERR_ARG, "sonar_noise_params_apply: fix_invalid / normalized need the scan launch's partials");
@@ -451,7 +384,10 @@ extern "C" int sonar_noise_params_apply(int src_dtype, const void* src, int dst_
     }
     const bool vec = plane_in % 4 == 0 && plane_out % 4 == 0 && aligned16(src) && aligned16(out);
     const hipStream_t st = (hipStream_t)stream;
-    if (src_dtype == SONAR_DTYPE_F32) return apply_src<float>(dst_dtype, src, out, planes, plane_in, plane_out, fix, norm, factor, threshold_std_devs, partials, npart, vec, st);
-    if (src_dtype == SONAR_DTYPE_F16) return apply_src<H16>(dst_dtype, src, out, planes, plane_in, plane_out, fix, norm, factor, threshold_std_devs, partials, npart, vec, st);
-    return apply_src<B16>(dst_dtype, src, out, planes, plane_in, plane_out, fix, norm, factor, threshold_std_devs, partials, npart, vec, st);
+    return with_dtype(src_dtype, "sonar_noise_params_apply", [&](auto from) {
+        return with_dtype(dst_dtype, "sonar_noise_params_apply", [&](auto to) {
+            return apply_typed<typename decltype(from)::type, typename decltype(to)::type>(src, out, planes, plane_in, plane_out, fix, norm, factor,
+                                                                                           threshold_std_devs, partials, npart, vec, st);
+        });
+    });
 }

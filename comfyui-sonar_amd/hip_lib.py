@@ -365,6 +365,13 @@ def _opt(t: Optional[torch.Tensor], name: str, dtype=torch.float32):
     return None if t is None else _dev(t, name, dtype)
 
 
+def _dtype_id(dtype, what: str) -> int:
+    """The SONAR_DTYPE_* code of ``dtype`` for the entry points that take one (csrc/dtype_io.h)."""
+    if dtype not in DTYPE_IDS:
+        raise SonarHipError(f"{what}: float32 / float16 / bfloat16 only (got {dtype})")
+    return DTYPE_IDS[dtype]
+
+
 def new_partials(device) -> torch.Tensor:
     """Workspace for the (sum, sumsq) partial pairs of one normalisation point."""
     return torch.empty(NPART * 2, dtype=torch.float64, device=device)
@@ -504,8 +511,7 @@ def cfg_op_prepare(x: Optional[torch.Tensor], t1: torch.Tensor, t2: Optional[tor
     or one per sample; the prediction flip), f(t) = t without; returns fp32 (f(t1) - f(t2), f(t2)), or (f(t1), None) without t2.  x, t1
     and t2 share one dtype (float32 / float16 / bfloat16) and are not written."""
     dtype = t1.dtype
-    if dtype not in DTYPE_IDS:
-        raise SonarHipError(f"cfg_op_prepare: expected float32, float16 or bfloat16, got {dtype}")
+    dtype_id = _dtype_id(dtype, "cfg_op_prepare")
     for name, t in (("x", x if sigma is not None else None), ("t2", t2)):
         if t is not None and t.shape != t1.shape:
             raise SonarHipError(f"cfg_op_prepare: shape mismatch, {name} {tuple(t.shape)} vs t1 {tuple(t1.shape)}")
@@ -515,7 +521,7 @@ def cfg_op_prepare(x: Optional[torch.Tensor], t1: torch.Tensor, t2: Optional[tor
     result = torch.empty(t1.shape, dtype=torch.float32, device=t1.device)
     t2_out = None if t2 is None else torch.empty_like(result)
     _check(
-        load().sonar_cfg_op_prepare(DTYPE_IDS[dtype], None if sigma is None else _dev(x, "x", dtype), _dev(t1, "t1", dtype), _opt(t2, "t2", dtype),
+        load().sonar_cfg_op_prepare(dtype_id, None if sigma is None else _dev(x, "x", dtype), _dev(t1, "t1", dtype), _opt(t2, "t2", dtype),
                                     psigma, sigma_n, _dev(result, "result"), _opt(t2_out, "t2_out"), t1.numel(), inner, _stream()),
         "sonar_cfg_op_prepare",
     )
@@ -527,8 +533,7 @@ def cfg_op_finish(result: torch.Tensor, t2f: Optional[torch.Tensor], x: Optional
     """... and after them, one launch: r = result + t2f; with a sigma r = x - sigma * r; returns blend(t1_orig, r, w) (``mode`` of
     BLEND_IDS), or r for mode None / "none", as a new tensor of t1_orig's dtype.  result and t2f are the fp32 tensors of cfg_op_prepare."""
     dtype = t1_orig.dtype
-    if dtype not in DTYPE_IDS:
-        raise SonarHipError(f"cfg_op_finish: expected float32, float16 or bfloat16, got {dtype}")
+    dtype_id = _dtype_id(dtype, "cfg_op_finish")
     for name, t in (("t2f", t2f), ("x", x if sigma is not None else None), ("t1_orig", t1_orig)):
         if t is not None and t.shape != result.shape:
             raise SonarHipError(f"cfg_op_finish: shape mismatch, {name} {tuple(t.shape)} vs result {tuple(result.shape)}")
@@ -538,7 +543,7 @@ def cfg_op_finish(result: torch.Tensor, t2f: Optional[torch.Tensor], x: Optional
     psigma, sigma_n, inner = _cfg_op_sigma(sigma, result, "cfg_op_finish")
     out = torch.empty_like(t1_orig)
     _check(
-        load().sonar_cfg_op_finish(DTYPE_IDS[dtype], _dev(result, "result"), _opt(t2f, "t2f"), None if sigma is None else _dev(x, "x", dtype),
+        load().sonar_cfg_op_finish(dtype_id, _dev(result, "result"), _opt(t2f, "t2f"), None if sigma is None else _dev(x, "x", dtype),
                                    psigma, sigma_n, _dev(t1_orig, "t1_orig", dtype), blend_id, float(w), _dev(out, "out", dtype),
                                    result.numel(), inner, _stream()),
         "sonar_cfg_op_finish",
@@ -2325,8 +2330,7 @@ def noise_params_tail(src: torch.Tensor, out_shape, out_dtype, planes: int, plan
     """The tail of CustomNoiseParametersNoise (csrc/noise_params.hip): ``src`` is ``planes`` planes of ``plane_in`` values (fp32 / fp16 /
     bf16), the first ``plane_out`` of each are kept; fix_invalid -> crop -> ``out_dtype`` -> scale_noise(factor, normalized), as a scan
     launch (skipped when neither flag is set) and an apply launch.  Returns a new tensor of ``out_shape``."""
-    if src.dtype not in DTYPE_IDS or out_dtype not in DTYPE_IDS:
-        raise SonarHipError(f"noise_params_tail: float32 / float16 / bfloat16 only (got {src.dtype} -> {out_dtype})")
+    src_id, out_id = _dtype_id(src.dtype, "noise_params_tail"), _dtype_id(out_dtype, "noise_params_tail")
     if planes * plane_in != src.numel() or not 0 < plane_out <= plane_in:
         raise SonarHipError(f"noise_params_tail: {planes} planes of {plane_in} (kept: {plane_out}) do not describe {src.numel()} values")
     out = torch.empty(out_shape, dtype=out_dtype, device=src.device)
@@ -2337,9 +2341,9 @@ def noise_params_tail(src: torch.Tensor, out_shape, out_dtype, planes: int, plan
     partials = None
     if fix_invalid or normalized:
         partials = torch.empty(lib.sonar_noise_params_ws_doubles(), dtype=torch.float64, device=src.device)
-        _check(lib.sonar_noise_params_scan(DTYPE_IDS[src.dtype], sp, planes, plane_in, plane_out, int(bool(fix_invalid)),
+        _check(lib.sonar_noise_params_scan(src_id, sp, planes, plane_in, plane_out, int(bool(fix_invalid)),
                                            _dev(partials, "partials", torch.float64), _stream()), "sonar_noise_params_scan")
-    _check(lib.sonar_noise_params_apply(DTYPE_IDS[src.dtype], sp, DTYPE_IDS[out_dtype], op, planes, plane_in, plane_out, int(bool(fix_invalid)),
+    _check(lib.sonar_noise_params_apply(src_id, sp, out_id, op, planes, plane_in, plane_out, int(bool(fix_invalid)),
                                         int(bool(normalized)), float(factor), float(threshold_std_devs), _opt(partials, "partials", torch.float64),
                                         _stream()), "sonar_noise_params_apply")
     return out
@@ -2364,8 +2368,7 @@ def freeu_layout(x: torch.Tensor, what: str = "freeu"):
         raise SonarHipError(f"{what}: expected a feature map [B, C, H, W]")
     if x.dtype == torch.float64:
         raise NotImplementedError(f"{what}: float64 feature maps are not built in (float32 / float16 / bfloat16)")
-    if x.dtype not in DTYPE_IDS:
-        raise SonarHipError(f"{what}: float32 / float16 / bfloat16 only (got {x.dtype})")
+    _dtype_id(x.dtype, what)
     if not x.is_cuda:
         raise SonarHipError(f"{what}: tensor lives on {x.device}; the Sonar HIP path only runs on a ROCm device")
     B, Cn, H, W = x.shape
