@@ -130,6 +130,7 @@ SIGNATURES = {
     "sonar_perlin_noise_ahead_ok": (_I, [_I64, _I64, _I64]),
     "sonar_perlin_noise_ahead_f32": (_I, [_P, _P, _I64, _I64, _F, _U64, _U64, _I64, _F, _F, _P, _I, _U64, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _U64, _P]),
     "sonar_resample_acc_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _F, _I, _I, _P, _P]),
+    "sonar_bislerp_acc_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sonar_pyramid_generate_f32": (_I, [_P, _I64, _I64, _I64, _I64, C.POINTER(_P), _PI64, _PI64, _PF, _I, _U64, _U64, _I64, _P, _P]),
     "sonar_pyramid_route": (_I, [_I64, _I64, _I64, _PI64, _PI64, _I, _I64]),
     "sonar_pyramid_noise_f32": (_I, [_P, _I64, _I64, _I64, _I64, C.POINTER(_P), _PI64, _PI64, _PF, _I, _U64, _U64, _I64, _F, _F, _P, _P]),
@@ -1162,6 +1163,63 @@ def resample_acc_(dst: torch.Tensor, src: torch.Tensor, scale: float, mode: str 
         "sonar_resample_acc_f32",
     )
     return dst
+
+
+BISLERP = "bislerp"                       # ComfyUI's resampler of C-vectors (csrc/bislerp.hip): not an F.interpolate mode, not in UPSCALE_MODES
+LEVEL_MODES = UPSCALE_MODES + (BISLERP,)  # what the pyramid generators take as `upscale_mode` (`level_acc_`)
+_bislerp_tables: dict = {}                # (old, new, device) -> (c1, c2, ratio) on the device, a few hundred bytes each
+
+
+def bislerp_axis(old: int, new: int):
+    """One axis of ComfyUI's ``bislerp`` (``generate_bilinear_data``): for each of ``new`` output positions the two source indices (int64) and
+    the interpolation ratio (fp32), from torch's own bilinear coordinates (``align_corners=False``) on the host.  A function of (old, new)."""
+    F = torch.nn.functional
+    c1f = F.interpolate(torch.arange(old, dtype=torch.float32).reshape(1, 1, 1, old), size=(1, new), mode="bilinear")
+    ratio = c1f - c1f.floor()
+    nxt = torch.arange(old, dtype=torch.float32).reshape(1, 1, 1, old) + 1
+    nxt[:, :, :, -1] -= 1
+    c2f = F.interpolate(nxt, size=(1, new), mode="bilinear")
+    return c1f.to(torch.int64).reshape(new), c2f.to(torch.int64).reshape(new), ratio.reshape(new)
+
+
+def bislerp_tables(old: int, new: int, device):
+    """``bislerp_axis(old, new)`` as device tensors (int32 indices, fp32 ratio), cached per (old, new, device)."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(old), int(new), device)
+    tab = _bislerp_tables.get(key)
+    if tab is None:
+        c1, c2, ratio = bislerp_axis(int(old), int(new))
+        tab = _bislerp_tables[key] = (c1.to(torch.int32).to(device), c2.to(torch.int32).to(device), ratio.to(device))
+    return tab
+
+
+def bislerp_acc_(dst: torch.Tensor, src: torch.Tensor, scale: float, accumulate: bool = True, partials=None) -> torch.Tensor:
+    """dst[N, C, H, W] (+)= bislerp(src[N, C, h, w]) * scale (``sonar_bislerp_acc_f32``: the slerp runs over dim 1)"""
+    if src.ndim != 4:
+        raise SonarHipError("bislerp_acc: the source is [N, C, h, w]")
+    N, Cn, h, w = src.shape
+    H, W = dst.shape[-2:]
+    if dst.numel() != N * Cn * H * W:
+        raise SonarHipError("bislerp_acc: batch / channel count mismatch")
+    c1w, c2w, rw = bislerp_tables(w, W, src.device)
+    c1h, c2h, rh = bislerp_tables(h, H, src.device)
+    _check(
+        load().sonar_bislerp_acc_f32(_dev(dst, "dst"), _dev(src, "src"), N, Cn, H, W, h, w, float(scale), int(bool(accumulate)),
+                                     _dev(c1w, "c1w", torch.int32), _dev(c2w, "c2w", torch.int32), _dev(rw, "rw"),
+                                     _dev(c1h, "c1h", torch.int32), _dev(c2h, "c2h", torch.int32), _dev(rh, "rh"),
+                                     _opt(partials, "partials", torch.float64), _stream()),
+        "sonar_bislerp_acc_f32",
+    )
+    return dst
+
+
+def level_acc_(dst: torch.Tensor, src: torch.Tensor, scale: float, mode: str, accumulate: bool = True, partials=None) -> torch.Tensor:
+    """A pyramid level [N, C, h, w] resampled into the latent: ``resample_acc_`` for the F.interpolate modes, ``bislerp_acc_`` for bislerp."""
+    if mode == BISLERP:
+        return bislerp_acc_(dst, src, scale, accumulate, partials)
+    return resample_acc_(dst, src, scale, mode, accumulate, partials)
 
 
 def _pyramid_args(levels):

@@ -537,7 +537,7 @@ class PyramidNoiseGenerator(FramesToChannelsNoiseGenerator):
 
     def generate(self, *_args):
         mode = self.upscale_mode
-        if mode not in hip_lib.UPSCALE_MODES:
+        if mode not in hip_lib.LEVEL_MODES:
             raise NotImplementedError(f"pyramid upscale_mode {mode!r} is not on the HIP path")
         b, c, h, w = self.get_adjusted_shape()
         partials = hip_lib.new_partials(self.device)
@@ -546,11 +546,11 @@ class PyramidNoiseGenerator(FramesToChannelsNoiseGenerator):
             pending = None
             for i, ch, cw in self._plan(h, w, lambda: torch.rand(1, generator=self.generator).item() * 2 + 2):
                 if pending is not None:
-                    hip_lib.resample_acc_(noise, *pending)
+                    hip_lib.level_acc_(noise, *pending)
                 level = tensor_to(torch.randn(b, c, ch, cw, dtype=torch.float32), self.device)
                 pending = (level, self.discount**i, mode, True)
             if pending is not None:
-                hip_lib.resample_acc_(noise, *pending, partials)  # last level also reduces the statistics
+                hip_lib.level_acc_(noise, *pending, partials)  # last level also reduces the statistics
             else:
                 partials = None
             return self.fix_output_frames(attach_stats(noise, partials))
@@ -624,25 +624,25 @@ class PyramidNoiseGenerator(FramesToChannelsNoiseGenerator):
                 levels.append((grid, ch, cw, self.discount**i))
         if fusable:
             return run(levels)
-        # rare odd widths / modes: same values through the unfused kernels
+        # rare odd widths / modes (nearest, bicubic, bislerp): same values through the unfused kernels
         out = hip_lib.philox_normal((b, c, h, w), self.device, seed, stream, offs)
         for grid, ch, cw, wt in levels:
             if grid is None:
                 grid = hip_lib.philox_normal((b, c, h, w), self.device, seed, stream + 1, offs)
-            hip_lib.resample_acc_(out, grid, wt, mode, True)
+            hip_lib.level_acc_(out, grid.view(b, c, ch, cw), wt, mode, True)
         if fused_factor is not None:
             return hip_lib.scale_noise_(out, fused_factor, True, hip_lib.stats(out))
         return attach_stats(out, hip_lib.stats(out, partials))
 
     def generate_normalized(self, factor, *_args):
-        if self.cpu or self.normalize_dims is not None or self.upscale_mode not in hip_lib.UPSCALE_MODES:
+        if self.cpu or self.normalize_dims is not None or self.upscale_mode not in hip_lib.LEVEL_MODES:
             return None
         return self.fix_output_frames(self._device_generate(None, factor))
 
     def generate_raw_stats(self, *_args):
         """(raw noise, its statistics partials) -- what ``generate_normalized`` computes before its in-place normalisation pass, for a
         consumer that applies the normalisation itself while reading the noise (``NoiseSampler.deferred``); None when not applicable."""
-        if self.cpu or self.normalize_dims is not None or self.upscale_mode not in hip_lib.UPSCALE_MODES:
+        if self.cpu or self.normalize_dims is not None or self.upscale_mode not in hip_lib.LEVEL_MODES:
             return None
         partials = hip_lib.new_partials(self.device)
         out = self._device_generate(partials, None)
@@ -668,7 +668,7 @@ class HighresPyramidNoiseGenerator(FramesToChannelsNoiseGenerator):
 
     def generate(self, s, sn):
         mode = self.upscale_mode
-        if mode not in hip_lib.UPSCALE_MODES:
+        if mode not in hip_lib.LEVEL_MODES:
             raise NotImplementedError(f"highres_pyramid upscale_mode {mode!r} is not on the HIP path")
         b, c, h, w = self.get_adjusted_shape()
         noise = self.noise_generator(s, sn).reshape(b, c, h, w)
@@ -687,12 +687,12 @@ class HighresPyramidNoiseGenerator(FramesToChannelsNoiseGenerator):
             # normal keyed by its global element index and only the taps the shrinking interpolation reads are drawn
             seed, stream = self.device_key(max(len(sizes), 1))
             plane_offset = current_batch_offset() * c
-            if hip_lib.levels_sampled((b, c, h, w), self.device, [(lh, lw, wt, 1.0) for lh, lw, wt in sizes], mode, seed, stream, plane_offset,
-                                      out=noise) is None:
+            if mode == hip_lib.BISLERP or hip_lib.levels_sampled((b, c, h, w), self.device, [(lh, lw, wt, 1.0) for lh, lw, wt in sizes], mode, seed,
+                                                                 stream, plane_offset, out=noise) is None:
                 for i, (lh, lw, wt) in enumerate(sizes):  # area off whole multiples: the windows overlap, the level is drawn (tile streams:
-                    # the cheaper generator when every value is needed) and pooled
+                    # the cheaper generator when every value is needed) and pooled; bislerp: a slerp reads whole C-vectors, the level is drawn
                     level = hip_lib.philox_normal((b, c, lh, lw), self.device, seed, stream + i, plane_offset * lh * lw)
-                    hip_lib.resample_acc_(noise, level, wt, mode, True)
+                    hip_lib.level_acc_(noise, level, wt, mode, True)
                     del level
             return self.fix_output_frames(noise)
         for lh, lw, wt in sizes:
@@ -701,7 +701,7 @@ class HighresPyramidNoiseGenerator(FramesToChannelsNoiseGenerator):
             else:
                 seed, stream = self.device_key()
                 level = hip_lib.philox_normal((b, c, lh, lw), self.device, seed, stream, current_batch_offset() * c * lh * lw)
-            hip_lib.resample_acc_(noise, level, wt, mode, True)
+            hip_lib.level_acc_(noise, level, wt, mode, True)
         return self.fix_output_frames(noise)
 
 
@@ -717,7 +717,7 @@ class PyramidOldNoiseGenerator(FramesToChannelsNoiseGenerator):
 
     def generate(self, *_args):
         mode = self.upscale_mode
-        if mode not in hip_lib.UPSCALE_MODES:
+        if mode not in hip_lib.LEVEL_MODES:
             raise NotImplementedError(f"pyramid_old upscale_mode {mode!r} is not on the HIP path")
         b, c, h, w = self.get_adjusted_shape()
         if not self.cpu:
@@ -727,12 +727,13 @@ class PyramidOldNoiseGenerator(FramesToChannelsNoiseGenerator):
             seed, stream = self.device_key(max(self.iterations, 1))
             plane_offset = current_batch_offset() * c
             levels = [(h * (2 << i), w * (2 << i), self.discount**i, 0.5**i) for i in range(self.iterations)]
-            out = hip_lib.levels_sampled((b, c, h, w), self.device, levels, mode, seed, stream, plane_offset)
+            # (bislerp: a slerp reads whole C-vectors of the level, which is drawn -- from the same keys -- and resampled)
+            out = None if mode == hip_lib.BISLERP else hip_lib.levels_sampled((b, c, h, w), self.device, levels, mode, seed, stream, plane_offset)
             if out is None:
                 out = torch.zeros((b, c, h, w), dtype=torch.float32, device=self.device)
                 for i, (lh, lw, weight, sd) in enumerate(levels):
                     level = hip_lib.level_normal((b, c, lh, lw), self.device, sd, seed, stream + i, plane_offset)
-                    hip_lib.resample_acc_(out, level, weight, mode, True)
+                    hip_lib.level_acc_(out, level, weight, mode, True)
                     del level
             return self.fix_output_frames(out)
         noise = torch.zeros((b, c, h, w), dtype=torch.float32, device=self.device)
@@ -740,7 +741,7 @@ class PyramidOldNoiseGenerator(FramesToChannelsNoiseGenerator):
         for i in range(self.iterations):
             r *= 2
             level = tensor_to(torch.normal(mean=0, std=0.5**i, size=(b, c, h * r, w * r), dtype=torch.float32, generator=self.generator), self.device)
-            hip_lib.resample_acc_(noise, level, self.discount**i, mode, True)
+            hip_lib.level_acc_(noise, level, self.discount**i, mode, True)
         return self.fix_output_frames(noise)
 
 

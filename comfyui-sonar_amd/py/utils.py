@@ -7,6 +7,7 @@ evaluates the thresholds on device, so there is no ``.item()`` host sync.
 from __future__ import annotations
 
 import contextlib
+import os
 import threading
 from typing import Callable, Optional, Sequence
 
@@ -17,6 +18,10 @@ from .. import hip_lib
 Tensor = torch.Tensor
 
 UPSCALE_METHODS = ("bilinear", "nearest-exact", "nearest", "area", "bicubic", "bislerp", "adaptive_avg_pool2d")
+
+# scale_samples(mode="bislerp") -- and with it ResizedNoise's upscale_mode / downscale_mode -- runs utils.bislerp only with this switch on;
+# off, it keeps refusing as before (the pyramid generators and utils.bislerp take the mode either way)
+BISLERP_IN_SCALE_SAMPLES = os.environ.get("SONAR_BISLERP_SCALE", "0") != "0"
 
 _STATS_ATTR = hip_lib.STATS_ATTR
 
@@ -177,15 +182,32 @@ def dims_restore(t: Tensor, inverse) -> Tensor:
     return t if inverse is None else t.permute(inverse).contiguous()
 
 
+def bislerp(samples: Tensor, width: int, height: int) -> Tensor:
+    """ComfyUI's ``comfy.utils.bislerp(samples, width, height)`` on the device (csrc/bislerp.hip): the C-vector of every pixel of
+    ``samples`` [N, C, h, w] resampled by spherical interpolation, along the width and then along the height.  Any float dtype, contiguous or
+    strided; computed in fp32, returned in the input's dtype.  ComfyUI is not vendored by the reference: **parity unpinned**, the
+    definition is restated in DESIGN.md and pinned by tests/bislerp_refs.py."""
+    _require_device(samples, "bislerp")
+    if samples.ndim != 4:
+        raise hip_lib.SonarHipError(f"bislerp: expects [N, C, h, w], got {tuple(samples.shape)}")
+    src = as_f32(samples)
+    out = torch.empty((*src.shape[:2], height, width), dtype=torch.float32, device=src.device)
+    hip_lib.bislerp_acc_(out, src, 1.0, accumulate=False)
+    return out if samples.dtype == torch.float32 else out.to(samples.dtype)
+
+
 def scale_samples(samples: Tensor, width: int, height: int, *, mode: str = "bicubic") -> Tensor:
     """py/utils.py:58-67: ``F.interpolate(samples, size=(height, width), mode=mode)`` on the HIP resampler (bilinear / nearest /
-    nearest-exact / bicubic / area / adaptive_avg_pool2d)."""
+    nearest-exact / bicubic / area / adaptive_avg_pool2d).  ``bislerp`` only with ``BISLERP_IN_SCALE_SAMPLES`` (off by default:
+    SONAR_BISLERP_SCALE=1 in the environment); the pyramid generators and ``bislerp`` itself do not depend on the switch."""
     _require_device(samples, "scale_samples")
     if mode in hip_lib.UPSCALE_MODES:
         src = as_f32(samples)
         out = torch.empty((*src.shape[:-2], height, width), dtype=torch.float32, device=src.device)
         hip_lib.resample_acc_(out, src, 1.0, mode, accumulate=False)
         return out if samples.dtype == torch.float32 else out.to(samples.dtype)
+    if mode == hip_lib.BISLERP and BISLERP_IN_SCALE_SAMPLES:
+        return bislerp(samples, width, height)
     raise NotImplementedError(f"upscale mode {mode!r} needs ComfyUI's bislerp, which the reference does not vendor")
 
 

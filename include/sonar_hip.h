@@ -904,6 +904,20 @@ int sonar_levels_sampled_f32(float* out, int64_t planes, int64_t H, int64_t W, i
 int sonar_level_normal_f32(float* level, int64_t planes, int64_t h, int64_t w, float sd, uint64_t seed, uint64_t stream_id,
                            int64_t plane_offset, void* stream);
 
+/* dst[N][C][H][W] (+)= bislerp(src[N][C][h][w]) * scale: ComfyUI's comfy.utils.bislerp (the reference's common_upscale(..., "bislerp"),
+ * py/utils.py:58-67; not vendored by the reference: parity unpinned, the definition is restated in DESIGN.md).  The C-vector of a pixel is
+ * interpolated spherically, along the width and then along the height, in one launch:
+ *     T[n][:][y][X] = slerp(S[n][:][y][c1w[X]], S[n][:][y][c2w[X]], rw[X]),   O[n][:][Y][X] = slerp(T[n][:][c1h[Y]][X], T[n][:][c2h[Y]][X], rh[Y])
+ * with slerp(b1, b2, r) over the channel axis: unit vectors u = b / |b| (0 for a zero vector), dot = sum(u1 u2), om = acos(dot),
+ * (sin((1 - r) om) u1 + sin(r om) u2) / sin(om) * (|b1| (1 - r) + |b2| r); b1 where dot > 1 - 1e-5, b1 (1 - r) + b2 r where dot < 1e-5 - 1
+ * (the jumps at the two thresholds are the definition's).  c1w / c2w / rw [W] and c1h / c2h / rh [H] are device tables (indices into the
+ * source axis and the interpolation ratio), built on the host from torch's bilinear coordinates; an index outside the axis is clamped.  Any
+ * C > 0.  accumulate != 0: added to dst; partials (nullable): the (sum, sumsq) partials of the finished dst, as sonar_resample_acc_f32
+ * leaves them.  Conventions of sonar_resample_acc_f32: error codes, no allocation, asynchronous on `stream`. */
+int sonar_bislerp_acc_f32(float* dst, const float* src, int64_t N, int64_t C, int64_t H, int64_t W, int64_t h, int64_t w, float scale,
+                          int accumulate, const int32_t* c1w, const int32_t* c2w, const float* rw, const int32_t* c1h, const int32_t* c2h,
+                          const float* rh, double* partials /*nullable*/, void* stream);
+
 /* ---------------------------------------------------------------- power-law rFFT noise (row PW) */
 /* Which kernel family serves an H x W plane of the power-noise path: 1 = the fixed-size LDS FFT kernels (powers of two, 16..256),
  * 2 = the general-size kernels (any even H <= 512, even W <= 1024 with H*(W/2+1) + H + W <= 20224 complex values: two-factor table-twiddle DFTs in LDS;
