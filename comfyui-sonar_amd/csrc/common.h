@@ -412,14 +412,29 @@ __device__ __forceinline__ T blend(int mode, T a, T b, T t) {
 // sonar_row_affine_f32: op 0 (x - a) / b, op 1 x * b + a
 __device__ __forceinline__ float row_affine_value(int op, float x, float a, float b) { return op == 0 ? (x - a) / b : x * b + a; }
 
+// the tail of a row's or group's fp64 (sum, sumsq) of n values: mean = s / n, unbiased std (n == 1: 0 / 0 = NaN like torch; a variance
+// that rounding made negative is 0)
+struct MeanStd {
+    float mean, stdv;
+};
+__device__ __forceinline__ MeanStd mean_std_of(double s, double q, double nt) {
+    const double m = s / nt;
+    const double var = (q - s * m) / (nt - 1.0);
+    return MeanStd{(float)m, (float)sqrt(var > 0.0 || !(var == var) ? var : 0.0)};
+}
+
 // normalize_to_scale's tail (py/utils.py:462-469): ((x - lo) / ((hi - lo) + eps)) * (tmax - tmin) + tmin, clamped; each step rounded
 // on its own as the reference's in-place tensor ops are.  The targets are Python floats there: their difference is formed in double
-// and rounded to fp32 ONCE (`span`; 0.3 - 0.1 is 0.2, not 0.20000002)
-__device__ __forceinline__ float minmax_rescale_value(float x, float lo, float hi, float eps, float tmin, float tmax, float span) {
-    const float denom = __fadd_rn(__fsub_rn(hi, lo), eps);
+// and rounded to fp32 ONCE (`span`; 0.3 - 0.1 is 0.2, not 0.20000002).  In two halves for the kernels that form the denominator once
+// per row or sample.
+__device__ __forceinline__ float minmax_rescale_denom(float lo, float hi, float eps) { return __fadd_rn(__fsub_rn(hi, lo), eps); }
+__device__ __forceinline__ float minmax_rescale_by(float x, float lo, float denom, float tmin, float tmax, float span) {
     float v = __fsub_rn(x, lo) / denom;
     v = __fadd_rn(__fmul_rn(v, span), tmin);
     return v != v ? v : fminf(fmaxf(v, tmin), tmax);  // clamp_ keeps NaN
+}
+__device__ __forceinline__ float minmax_rescale_value(float x, float lo, float hi, float eps, float tmin, float tmax, float span) {
+    return minmax_rescale_by(x, lo, minmax_rescale_denom(lo, hi, eps), tmin, tmax, span);
 }
 
 }  // namespace sonar

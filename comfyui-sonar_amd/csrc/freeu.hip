@@ -19,6 +19,7 @@
 
 #include "dtype_io.h"
 #include "power_any_core.h"
+#include "range_reduce.h"
 
 namespace sonar {
 namespace freeu {
@@ -171,8 +172,7 @@ constexpr int kExtThreads = 1024;
 __global__ void __launch_bounds__(kExtThreads) hidden_extremes_kernel(float* __restrict__ mean, int64_t HW, float* __restrict__ extremes,
                                                                       const float* __restrict__ ws, int groups, int64_t C) {
     kernarg_touch_for(mean, HW, extremes, ws, groups, C);
-    __shared__ float slo[kExtThreads / 64], shi[kExtThreads / 64];
-    __shared__ int snan[kExtThreads / 64];
+    __shared__ float red[3 * kExtThreads / 64];
     float* m = mean + (int64_t)blockIdx.x * HW;
     const int64_t B = gridDim.x;
     float lo = INFINITY, hi = -INFINITY;
@@ -191,22 +191,10 @@ __global__ void __launch_bounds__(kExtThreads) hidden_extremes_kernel(float* __r
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off));
-        hi = fmaxf(hi, __shfl_xor(hi, off));
-        nan |= __shfl_xor(nan, off);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) slo[w] = lo, shi[w] = hi, snan[w] = nan;
-    __syncthreads();
+    block_minmax_nan<kExtThreads>(lo, hi, nan, red);  // a NaN poisons both
     if (threadIdx.x == 0) {
-        for (int k = 1; k < kExtThreads / 64; ++k) {
-            lo = fminf(lo, slo[k]);
-            hi = fmaxf(hi, shi[k]);
-            nan |= snan[k];
-        }
-        extremes[2 * blockIdx.x] = nan ? NAN : lo;
-        extremes[2 * blockIdx.x + 1] = nan ? NAN : hi;
+        extremes[2 * blockIdx.x] = nan_poisons(nan, lo);
+        extremes[2 * blockIdx.x + 1] = nan_poisons(nan, hi);
     }
 }
 

@@ -17,8 +17,9 @@
 // adds them in slice order: a function of the shape alone, so two runs give the same bits (no atomics).
 //
 // Accumulation: rowstats_kernel's (rows.hip) -- sum and sum of squares in fp64 (a product of two floats is exact in a double), mean
-// = s / n, var = (q - s * mean) / (n - 1), the same last lines (finish_mean_std) -- with the partial sums of lanes, waves and slices added
-// in fp64 in a fixed order.  n == 1 gives 0 / 0 = NaN like torch.  Min / max are fminf / fmaxf folds as in minmax_rows_kernel.
+// = s / n, var = (q - s * mean) / (n - 1), the one tail both share (mean_std_of, common.h) -- with the partial sums of lanes, waves and
+// slices added in fp64 in a fixed order.  n == 1 gives 0 / 0 = NaN like torch.  Min / max are fminf / fmaxf folds as in minmax_rows_kernel
+// (a NaN never wins), the peak torch.amax's (a NaN poisons); a wave joins its lanes through range_reduce.h, where both rules are stated.
 //
 // The same two sweeps carry two more per-group results (the `X` parameter of the kernels):
 //   peak          amax of x or of |x| with torch.amax's NaN (amax_mid_kernel's fold): PowerLawNoiseGenerator's div_max_dims over any dims,
@@ -26,6 +27,7 @@
 //   divided mean  the mean of x / d[g], every quotient rounded to fp32 first and added in fp64: scale_rows_kernel's second statistic, so
 //                 that scale_noise(normalize_dims=...) over any dims is group_stats (std) -> divided mean -> group_scale_noise_kernel.
 #include "common.h"
+#include "range_reduce.h"
 
 namespace sonar {
 namespace {
@@ -107,16 +109,8 @@ struct Acc {
         nan |= v != v;
         hi = fmaxf(hi, v);
     }
-    __device__ __forceinline__ float peak() const { return nan ? NAN : hi; }  // torch.amax propagates NaN
+    __device__ __forceinline__ float peak() const { return nan_poisons(nan, hi); }  // torch.amax propagates NaN
 };
-
-// rowstats_kernel's last lines
-__device__ __forceinline__ void finish_mean_std(double s, double q, uint32_t n, float* mean, float* stdv) {
-    const double nt = (double)n, m = s / nt;
-    const double var = (q - s * m) / (nt - 1.0);
-    *mean = (float)m;
-    *stdv = (float)sqrt(var > 0.0 || !(var == var) ? var : 0.0);
-}
 
 // what a (group, slice) leaves: the final values (S == 1) or its partials, plane p of the workspace at ws[(p * S + slice) * G + g]
 // (kPeak / kPeakAbs: the peak goes to hi, one plane; kDivMean: the mean to `mean`, one plane)
@@ -133,7 +127,11 @@ __device__ __forceinline__ void leave(const Acc<MS, MM, X>& a, uint32_t g, uint3
         return;
     }
     if (S == 1) {
-        if constexpr (MS) finish_mean_std(a.s, a.q, R, mean + g, stdv + g);
+        if constexpr (MS) {
+            const MeanStd ms = mean_std_of(a.s, a.q, (double)R);
+            mean[g] = ms.mean;
+            stdv[g] = ms.stdv;
+        }
         if constexpr (MM) {
             lo[g] = a.lo;
             hi[g] = a.hi;
@@ -175,16 +173,13 @@ __global__ void __launch_bounds__(kBlock) group_stats_runs_kernel(const float* _
             a.s = wave_sum(a.s);
             if constexpr (X == kPlain) a.q = wave_sum(a.q);
         }
-        if constexpr (MM) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                a.lo = fminf(a.lo, __shfl_down(a.lo, off, 64));
-                a.hi = fmaxf(a.hi, __shfl_down(a.hi, off, 64));
-            }
+        if constexpr (MM) {  // a NaN never wins
+            a.lo = wave_min(a.lo);
+            a.hi = wave_max(a.hi);
         }
-        if constexpr (X == kPeak || X == kPeakAbs) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) a.fold(__shfl_down(a.peak(), off, 64));
+        if constexpr (X == kPeak || X == kPeakAbs) {  // a NaN poisons: the flag travels beside the maximum
+            a.hi = wave_max(a.hi);
+            a.nan = wave_or(a.nan) != 0;
         }
         if (lane == 0) leave<MS, MM, X>(a, g, sl, G, R, S, mean, stdv, lo, hi, ws);
     }
@@ -245,7 +240,11 @@ __global__ void __launch_bounds__(kBlock) group_stats_combine_kernel(const doubl
                 a.hi = fmaxf(a.hi, (float)ws[(MS ? 3 : 1) * plane + at]);
             }
         }
-        if constexpr (MS) finish_mean_std(a.s, a.q, R, mean + g, stdv + g);
+        if constexpr (MS) {
+            const MeanStd ms = mean_std_of(a.s, a.q, (double)R);
+            mean[g] = ms.mean;
+            stdv[g] = ms.stdv;
+        }
         if constexpr (MM) {
             lo[g] = a.lo;
             hi[g] = a.hi;

@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "range_reduce.h"
 
 namespace sonar {
 
@@ -30,13 +31,9 @@ struct ComposeArgs {
     float tmin, tmax, span, eps, multiplier, strength;
 };
 
-// normalize_to_scale's value sequence (the same as minmax_rescale_kernel, rows.hip), then `result *= noise_multiplier`
+// normalize_to_scale's value sequence (minmax_rescale_by, common.h), then `result *= noise_multiplier`
 __device__ __forceinline__ float prepare_noise(float n, bool normalize, float lo, float denom, const ComposeArgs& a) {
-    if (normalize) {
-        float v = __fsub_rn(n, lo) / denom;
-        v = __fadd_rn(__fmul_rn(v, a.span), a.tmin);
-        n = v != v ? v : fminf(fmaxf(v, a.tmin), a.tmax);  // clamp_ keeps NaN
-    }
+    if (normalize) n = minmax_rescale_by(n, lo, denom, a.tmin, a.tmax, a.span);
     return __fmul_rn(n, a.multiplier);
 }
 
@@ -46,25 +43,11 @@ __device__ __forceinline__ float blend_image(int mode, float img, float n, float
 
 __device__ __forceinline__ float clip01(float v) { return v != v ? v : fminf(fmaxf(v, 0.0f), 1.0f); }  // clip_ keeps NaN
 
-// block-wide (min, max) of the values the block wrote -> its partial slot
+// block-wide (min, max) of the values the block wrote -> its partial slot; a NaN never wins
 __device__ __forceinline__ void write_minmax_part(float lo, float hi, float* part_min, float* part_max, int64_t slot) {
-    __shared__ float smin[kBlock / 64], smax[kBlock / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off, 64));
-        hi = fmaxf(hi, __shfl_down(hi, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        smin[threadIdx.x >> 6] = lo;
-        smax[threadIdx.x >> 6] = hi;
-    }
-    __syncthreads();
+    __shared__ float red[2 * kBlock / 64];
+    block_minmax<kBlock>(lo, hi, red);
     if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w) {
-            lo = fminf(lo, smin[w]);
-            hi = fmaxf(hi, smax[w]);
-        }
         part_min[slot] = lo;
         part_max[slot] = hi;
     }
@@ -85,7 +68,7 @@ __global__ void __launch_bounds__(kBlock) image_compose_kernel(ComposeArgs a) {
     float lo = 0.0f, denom = 1.0f;
     if (normalize) {
         lo = a.noise_lo[b];
-        denom = __fadd_rn(__fsub_rn(a.noise_hi[b], lo), a.eps);
+        denom = minmax_rescale_denom(lo, a.noise_hi[b], a.eps);
     }
     float vlo = INFINITY, vhi = -INFINITY;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
@@ -165,34 +148,17 @@ __global__ void __launch_bounds__(kBlock) image_channel_mean_kernel(const float*
 __global__ void __launch_bounds__(kBlock) image_rescale_kernel(float* __restrict__ image, int64_t per_sample, const float* __restrict__ part_min,
                                                                 const float* __restrict__ part_max, int parts, float eps) {
     kernarg_touch_for(image, per_sample, part_min, part_max, parts, eps);
-    __shared__ float smin[kBlock / 64], smax[kBlock / 64];
+    __shared__ float red[2 * kBlock / 64];
     const int64_t b = blockIdx.y;
     float lo = INFINITY, hi = -INFINITY;
     for (int i = threadIdx.x; i < parts; i += kBlock) {
         lo = fminf(lo, part_min[b * SONAR_IMAGE_NPART + i]);
         hi = fmaxf(hi, part_max[b * SONAR_IMAGE_NPART + i]);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_xor(lo, off, 64));
-        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        smin[threadIdx.x >> 6] = lo;
-        smax[threadIdx.x >> 6] = hi;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-        lo = fminf(lo, smin[w]);
-        hi = fmaxf(hi, smax[w]);
-    }
-    const float denom = __fadd_rn(__fsub_rn(hi, lo), eps);
-    auto rescale = [&](float x) {
-        float v = __fsub_rn(x, lo) / denom;
-        v = __fadd_rn(__fmul_rn(v, 1.0f), 0.0f);
-        return v != v ? v : fminf(fmaxf(v, 0.0f), 1.0f);
-    };
+    block_minmax<kBlock>(lo, hi, red);  // a NaN never wins
+    const float denom = minmax_rescale_denom(lo, hi, eps);
+    // targets 0 and 1: the `* 1.0f + 0.0f` steps of the sequence are kept (a -0 becomes +0 as in the reference)
+    auto rescale = [&](float x) { return minmax_rescale_by(x, lo, denom, 0.0f, 1.0f, 1.0f); };
     float* row = image + b * per_sample;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     if ((reinterpret_cast<uintptr_t>(row) & 15u) == 0 && (per_sample & 3) == 0) {

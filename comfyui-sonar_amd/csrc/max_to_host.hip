@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "range_reduce.h"
 
 using namespace sonar;
 
@@ -14,8 +15,7 @@ using namespace sonar;
 __global__ void __launch_bounds__(kBlock) max_to_host_kernel(const float* __restrict__ x, int64_t n, unsigned long long* __restrict__ host_out,
                                                              unsigned ticket) {
     kernarg_touch_for(x, n, host_out, ticket);
-    __shared__ float part[kBlock / 64];
-    __shared__ int nan_part[kBlock / 64];
+    __shared__ float red[2 * kBlock / 64];
     float m = -INFINITY;
     int bad = 0;
     for (int64_t i = threadIdx.x; i < n; i += kBlock) {
@@ -23,21 +23,9 @@ __global__ void __launch_bounds__(kBlock) max_to_host_kernel(const float* __rest
         bad |= v != v;
         m = fmaxf(m, v);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        m = fmaxf(m, __shfl_xor(m, off));
-        bad |= __shfl_xor(bad, off);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        part[threadIdx.x >> 6] = m;
-        nan_part[threadIdx.x >> 6] = bad;
-    }
-    __syncthreads();
+    m = block_max_poisoned<kBlock>(m, bad, red);  // a NaN poisons
     if (threadIdx.x == 0) {
-        for (int w = 1; w < kBlock / 64; ++w) {
-            m = fmaxf(m, part[w]);
-            bad |= nan_part[w];
-        }
-        const unsigned long long word = ((unsigned long long)ticket << 32) | __float_as_uint(bad ? NAN : m);
+        const unsigned long long word = ((unsigned long long)ticket << 32) | __float_as_uint(m);
         __hip_atomic_store(host_out, word, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }

@@ -21,6 +21,7 @@
 
 #include "dtype_io.h"
 #include "ew_driver.h"  // aligned16
+#include "range_reduce.h"
 
 namespace sonar {
 namespace {
@@ -73,11 +74,8 @@ __device__ __forceinline__ void block_fold(double (&sum)[kSums], float& mx, floa
     constexpr int NW = kBlock / 64;
 #pragma unroll
     for (int k = 0; k < kSums; ++k) sum[k] = wave_sum(sum[k]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        mn = fminf(mn, __shfl_xor(mn, off, 64));
-    }
+    mx = wave_max(mx);  // over the finite values only (Seen::add): no NaN reaches these folds
+    mn = wave_min(mn);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (lane == 0) {
 #pragma unroll

@@ -3,7 +3,8 @@
 // including the map is one correctly rounded fp32 operation (or exact: min, max, fmod), written here in the reference's order, so the
 // argument of erfinv equals the reference's bit for bit; what follows is smooth ("Pattern-break").
 //
-// Two routes with bit-equal outputs (one device function per step, min and max exact in any order):
+// Two routes with bit-equal outputs (one device function per step; min and max exact in any order, folded by block_minmax of
+// range_reduce.h: a NaN never wins, as in sonar_minmax_rows_f32):
 //   three launches  pb_range_kernel          (lo, hi) of x, one pair of partials per block
 //                   pb_result_range_kernel   folds those, (lo, hi) of pb_result(x), one pair per block -- only with restore_scale
 //                   pb_apply_kernel          folds both sets, recomputes pb_result, rescales, blends, stores, (sum, sumsq) of the output
@@ -11,6 +12,7 @@
 // Nothing is read on the host.  The result is recomputed in the last launch instead of being stored by the second: 16 bytes of traffic per
 // element against 24.
 #include "common.h"
+#include "range_reduce.h"
 
 namespace sonar {
 
@@ -57,38 +59,6 @@ __device__ __forceinline__ float pb_result(float x, float lo, float hi, float de
     const float e = a <= -1.0f ? -INFINITY : (a >= 1.0f ? INFINITY : erfinvf(a));
     const float y = __fmul_rn(__fmul_rn(__fmul_rn(detail_scale, e), (float)1.4142135623730951), (float)0.2);
     return y != y ? y : fminf(fmaxf(y, -1.0f), 1.0f);  // clamp_ keeps NaN
-}
-
-// K (lo, hi) pairs reduced over the workgroup, the totals in every thread.  fminf / fmaxf: a NaN never wins, as in sonar_minmax_rows_f32.
-// `sm`: 2 K BLOCK / 64 floats.
-template <int BLOCK, int K>
-__device__ __forceinline__ void pb_block_minmax(float (&lo)[K], float (&hi)[K], float* sm) {
-    constexpr int NW = BLOCK / 64;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off, 64));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off, 64));
-        }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();  // the previous reduction's readers are done with `sm`
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            sm[(2 * k) * NW + wid] = lo[k];
-            sm[(2 * k + 1) * NW + wid] = hi[k];
-        }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        lo[k] = sm[(2 * k) * NW];
-        hi[k] = sm[(2 * k + 1) * NW];
-        for (int w = 1; w < NW; ++w) {
-            lo[k] = fminf(lo[k], sm[(2 * k) * NW + w]);
-            hi[k] = fmaxf(hi[k], sm[(2 * k + 1) * NW + w]);
-        }
-    }
 }
 
 struct PbRange {
@@ -162,7 +132,7 @@ __global__ void __launch_bounds__(kBlock) pb_range_kernel(const float* __restric
     __shared__ float sm[2 * kBlock / 64];
     const PbRange r = pb_range_of(x, L, (int64_t)blockIdx.x * kBlock + threadIdx.x, (int64_t)gridDim.x * kBlock);
     float lo[1] = {r.lo}, hi[1] = {r.hi};
-    pb_block_minmax<kBlock, 1>(lo, hi, sm);
+    block_minmax<kBlock, 1>(lo, hi, sm);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = lo[0];
         part[2 * blockIdx.x + 1] = hi[0];
@@ -178,10 +148,10 @@ __global__ void __launch_bounds__(kBlock) pb_result_range_kernel(const float* __
         lo[0] = fminf(lo[0], xpart[2 * i]);
         hi[0] = fmaxf(hi[0], xpart[2 * i + 1]);
     }
-    pb_block_minmax<kBlock, 1>(lo, hi, sm);
+    block_minmax<kBlock, 1>(lo, hi, sm);
     const PbRange r = pb_result_range_of(x, L, (int64_t)blockIdx.x * kBlock + threadIdx.x, (int64_t)gridDim.x * kBlock, lo[0], hi[0], detail_scale);
     float rlo[1] = {r.lo}, rhi[1] = {r.hi};
-    pb_block_minmax<kBlock, 1>(rlo, rhi, sm);
+    block_minmax<kBlock, 1>(rlo, rhi, sm);
     if (threadIdx.x == 0) {
         rpart[2 * blockIdx.x] = rlo[0];
         rpart[2 * blockIdx.x + 1] = rhi[0];
@@ -205,7 +175,7 @@ __global__ void __launch_bounds__(kBlock) pb_apply_kernel(const float* __restric
             lo[1] = fminf(lo[1], rpart[2 * i]);
             hi[1] = fmaxf(hi[1], rpart[2 * i + 1]);
         }
-    pb_block_minmax<kBlock, 2>(lo, hi, sm);
+    block_minmax<kBlock, 2>(lo, hi, sm);
     const PbApply A{lo[0], hi[0], lo[1], hi[1], pb_span(lo[0], hi[0]), detail_scale, percentage, mode};
     double s = 0.0, q = 0.0;
     pb_apply_to<RESTORE>(x, out, L, (int64_t)blockIdx.x * kBlock + threadIdx.x, (int64_t)gridDim.x * kBlock, A, s, q);
@@ -221,13 +191,13 @@ __global__ void __launch_bounds__(kPbOneBlock) pb_one_kernel(const float* __rest
     const int64_t tid = threadIdx.x;
     const PbRange r = pb_range_of(x, L, tid, kPbOneBlock);
     float lo[1] = {r.lo}, hi[1] = {r.hi};
-    pb_block_minmax<kPbOneBlock, 1>(lo, hi, sm);
+    block_minmax<kPbOneBlock, 1>(lo, hi, sm);
     float rlo[1] = {0.0f}, rhi[1] = {0.0f};
     if (RESTORE) {
         const PbRange rr = pb_result_range_of(x, L, tid, kPbOneBlock, lo[0], hi[0], detail_scale);
         rlo[0] = rr.lo;
         rhi[0] = rr.hi;
-        pb_block_minmax<kPbOneBlock, 1>(rlo, rhi, sm);
+        block_minmax<kPbOneBlock, 1>(rlo, rhi, sm);
     }
     const PbApply A{lo[0], hi[0], rlo[0], rhi[0], pb_span(lo[0], hi[0]), detail_scale, percentage, mode};
     double s = 0.0, q = 0.0;

@@ -6,6 +6,7 @@
 //   * rows of up to 64 Ki values stay in registers (VPT values per thread) across every pass: read once, written once;
 //   * longer rows are re-read from memory on every pass (same code, VPT = 0).
 #include "common.h"
+#include "range_reduce.h"
 
 namespace sonar {
 
@@ -113,19 +114,7 @@ __device__ __forceinline__ float q_finish_light(float o, bool centered, float ma
     return o;
 }
 
-// ---- block reductions ----------------------------------------------------------------------------------------------------------------
-template <int THREADS, typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, T* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T r = red[0];
-#pragma unroll 2
-    for (int w = 1; w < THREADS / 64; ++w) r = op(r, red[w]);
-    __syncthreads();
-    return r;
-}
+// (block reductions: block_reduce of range_reduce.h -- the totals in every thread, waves joined in ascending order)
 
 // ---- the row: in registers (VPT > 0) or re-read from memory (VPT == 0) --------------------------------------------------------------
 template <int THREADS, int VPT>

@@ -1,9 +1,12 @@
 // Per-row and per-mid-axis kernels: one workgroup per row (row_visit, SONAR_ROW_LAUNCH) or one thread per element with its row's
 // values broadcast -- row statistics, min/max and the rescales built on them, amax / std / division over a middle axis, the
 // ModulatedNoise gain and ratio mix, the |x| quantile per row with its clamp, and the periodic table multiply.
+// The folds shared with group_stats.hip's strided kernels live in headers: extremes and the NaN flag in range_reduce.h (which NaN rule a
+// kernel follows is said at its reduction), the mean / std tail (mean_std_of) and the rescale sequences in common.h.
 #include <math.h>
 
 #include "common.h"
+#include "range_reduce.h"
 
 namespace sonar {
 
@@ -56,11 +59,7 @@ __global__ void __launch_bounds__(THREADS) scale_rows_kernel(float* x, int64_t r
             s += v; q += v * v;
         });
         block_sum2<THREADS>(s, q, red);
-        if (threadIdx.x == 0) {
-            const double nt = (double)inner;
-            const double var = (q - s * (s / nt)) / (nt - 1.0);
-            sh_val = (float)sqrt(var > 0.0 || !(var == var) ? var : 0.0);
-        }
+        if (threadIdx.x == 0) sh_val = mean_std_of(s, q, (double)inner).stdv;
         __syncthreads();
         const float sd = sh_val;
         double s2 = 0.0, q2 = 0.0;
@@ -89,7 +88,7 @@ template <int THREADS>
 __global__ void __launch_bounds__(THREADS) minmax_rows_kernel(const float* __restrict__ x, int64_t rows, int64_t inner,
                                                               float* out_min, float* out_max) {
     kernarg_touch_for(x, rows, inner, out_min, out_max);
-    __shared__ float smin[THREADS / 64], smax[THREADS / 64];
+    __shared__ float red[2 * THREADS / 64];
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
         const float* row = x + r * inner;
         float lo = INFINITY, hi = -INFINITY;
@@ -97,25 +96,11 @@ __global__ void __launch_bounds__(THREADS) minmax_rows_kernel(const float* __res
             lo = fminf(lo, v);
             hi = fmaxf(hi, v);
         });
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            lo = fminf(lo, __shfl_down(lo, off, 64));
-            hi = fmaxf(hi, __shfl_down(hi, off, 64));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            smin[threadIdx.x >> 6] = lo;
-            smax[threadIdx.x >> 6] = hi;
-        }
-        __syncthreads();
+        block_minmax<THREADS>(lo, hi, red);  // a NaN never wins; its closing barrier frees `red` for the next row
         if (threadIdx.x == 0) {
-            for (int w = 1; w < THREADS / 64; ++w) {
-                lo = fminf(lo, smin[w]);
-                hi = fmaxf(hi, smax[w]);
-            }
             out_min[r] = lo;
             out_max[r] = hi;
         }
-        __syncthreads();
     }
 }
 
@@ -133,10 +118,9 @@ __global__ void __launch_bounds__(THREADS) rowstats_kernel(const float* __restri
         });
         block_sum2<THREADS>(s, q, red);
         if (threadIdx.x == 0) {
-            const double nt = (double)inner, m = s / nt;
-            const double var = (q - s * m) / (nt - 1.0);
-            mean[r] = (float)m;
-            stdv[r] = (float)sqrt(var > 0.0 || !(var == var) ? var : 0.0);
+            const MeanStd ms = mean_std_of(s, q, (double)inner);
+            mean[r] = ms.mean;
+            stdv[r] = ms.stdv;
         }
         __syncthreads();
     }
@@ -169,41 +153,22 @@ __global__ void __launch_bounds__(kBlock) minmax_rescale_kernel(const float* __r
 // own extremes.  Pass 1: per row (min, max) over the negatives and over the positives (+-inf where a sign has no value).
 __global__ void __launch_bounds__(kBlock) signed_minmax_rows_kernel(const float* __restrict__ x, int64_t rows, int64_t inner, float4* __restrict__ out) {
     kernarg_touch_for(x, rows, inner, out);
-    __shared__ float red[4][kBlock / 64];
+    __shared__ float red[4 * kBlock / 64];
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
-        float nlo = INFINITY, nhi = -INFINITY, plo = INFINITY, phi = -INFINITY;
+        float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};  // [0]: the negatives, [1]: the positives
         const float* row = x + r * inner;
         for (int64_t i = threadIdx.x; i < inner; i += kBlock) {
             const float v = row[i];
             if (v < 0.0f) {
-                nlo = fminf(nlo, v);
-                nhi = fmaxf(nhi, v);
+                lo[0] = fminf(lo[0], v);
+                hi[0] = fmaxf(hi[0], v);
             } else if (v > 0.0f) {
-                plo = fminf(plo, v);
-                phi = fmaxf(phi, v);
+                lo[1] = fminf(lo[1], v);
+                hi[1] = fmaxf(hi[1], v);
             }
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            nlo = fminf(nlo, __shfl_xor(nlo, off));
-            nhi = fmaxf(nhi, __shfl_xor(nhi, off));
-            plo = fminf(plo, __shfl_xor(plo, off));
-            phi = fmaxf(phi, __shfl_xor(phi, off));
-        }
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) {
-            const int w = threadIdx.x >> 6;
-            red[0][w] = nlo; red[1][w] = nhi; red[2][w] = plo; red[3][w] = phi;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < kBlock / 64; ++w) {
-                nlo = fminf(nlo, red[0][w]);
-                nhi = fmaxf(nhi, red[1][w]);
-                plo = fminf(plo, red[2][w]);
-                phi = fmaxf(phi, red[3][w]);
-            }
-            out[r] = make_float4(nlo, nhi, plo, phi);
-        }
+        block_minmax<kBlock, 2>(lo, hi, red);  // a NaN never wins; its closing barrier frees `red` for the next row
+        if (threadIdx.x == 0) out[r] = make_float4(lo[0], hi[0], lo[1], hi[1]);
     }
 }
 
@@ -230,10 +195,7 @@ __global__ void __launch_bounds__(kBlock) signed_rescale_kernel(const float* __r
                 const double tmin_d = neg ? min_neg : (min_pos < 0.0 ? (double)st.z : min_pos);
                 const double tmax_d = neg ? (max_neg >= 0.0 ? (double)st.y : max_neg) : max_pos;
                 const float span = (float)(tmax_d - tmin_d), tmin = (float)tmin_d, tmax = (float)tmax_d;
-                const float denom = __fadd_rn(__fsub_rn(hi, lo), eps);
-                float q = __fsub_rn(v, lo) / denom;
-                q = __fadd_rn(__fmul_rn(q, span), tmin);
-                res = q != q ? q : fminf(fmaxf(q, tmin), tmax);
+                res = minmax_rescale_value(v, lo, hi, eps, tmin, tmax, span);
             }
         } else if (v != v) {
             res = 0.0f;  // NaN is neither < 0 nor > 0: the reference's masks leave the zero of zeros_like
@@ -257,7 +219,7 @@ __global__ void __launch_bounds__(kBlock) amax_mid_kernel(const float* __restric
             nan |= v != v;
             hi = fmaxf(hi, v);
         }
-        peak[t] = nan ? NAN : hi;  // torch.amax propagates NaN
+        peak[t] = nan_poisons(nan, hi);  // torch.amax propagates NaN
     }
 }
 
@@ -266,8 +228,7 @@ template <int THREADS>
 __global__ void __launch_bounds__(THREADS) amax_row_kernel(const float* __restrict__ x, int64_t rows, int64_t len, int use_abs,
                                                                 float* peak) {
     kernarg_touch_for(x, rows, len, use_abs, peak);
-    __shared__ float smax[THREADS / 64];
-    __shared__ int snan[THREADS / 64];
+    __shared__ float red[2 * THREADS / 64];
     for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
         float hi = -INFINITY;
         int nan = 0;
@@ -276,24 +237,8 @@ __global__ void __launch_bounds__(THREADS) amax_row_kernel(const float* __restri
             nan |= v != v;
             hi = fmaxf(hi, v);
         });
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            hi = fmaxf(hi, __shfl_down(hi, off, 64));
-            nan |= __shfl_down(nan, off, 64);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            smax[threadIdx.x >> 6] = hi;
-            snan[threadIdx.x >> 6] = nan;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < THREADS / 64; ++w) {
-                hi = fmaxf(hi, smax[w]);
-                nan |= snan[w];
-            }
-            peak[r] = nan ? NAN : hi;
-        }
-        __syncthreads();
+        const float top = block_max_poisoned<THREADS>(hi, nan, red);  // a NaN poisons; its closing barrier frees `red` for the next row
+        if (threadIdx.x == 0) peak[r] = top;
     }
 }
 

@@ -13,6 +13,7 @@
 // library's -ffp-contract=off), so a difference lands on the side of the wrap where the reference's lands.  Square roots are sqrtf, the
 // correctly rounded one (the __fsqrt_rn of this toolchain is the native instruction, 1 ulp).
 #include "common.h"
+#include "range_reduce.h"
 
 namespace sonar {
 
@@ -217,7 +218,7 @@ __global__ void __launch_bounds__(kBlock) voronoi_octave_kernel(const float* __r
             const int64_t slot = PASS == 0 ? 0 : 1 + __shfl(row, 0);
             const bool mine = PASS == 0 || !live || row == slot - 1;
             if (__all(mine)) {
-                for (int m = 32; m >= 1; m >>= 1) tmin = fminf(tmin, __shfl_xor(tmin, m)), tmax = fmaxf(tmax, __shfl_xor(tmax, m));
+                tmin = wave_min(tmin), tmax = wave_max(tmax);  // a NaN never wins
                 if ((threadIdx.x & 63) == 0 && tmin <= tmax) atomicMin(fz.stats + 2 * slot, ordered(tmin)), atomicMax(fz.stats + 2 * slot + 1, ordered(tmax));
             } else if (live && tmin <= tmax) {
                 atomicMin(fz.stats + 2 + 2 * row, ordered(tmin)), atomicMax(fz.stats + 3 + 2 * row, ordered(tmax));
