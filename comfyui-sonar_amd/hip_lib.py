@@ -114,6 +114,8 @@ SIGNATURES = {
     "sonar_philox_noise_f32": (_I, [_I, _P, _I64, _U64, _U64, _I64, _F, _F, _F, _F, _F, _P, _P]),
     "sonar_philox_noise_ahead_ok": (_I, [_I, _I64, _F]),
     "sonar_philox_noise_ahead_f32": (_I, [_I, _P, _I64, _U64, _U64, _I64, _F, _F, _F, _F, _F, _P, _I, _U64, _P, _P]),
+    "sonar_philox_rows_max_inner": (_I64, []),
+    "sonar_philox_rows_f32": (_I, [_P, _I64, _I64, _P, _P, _I, _U64, _F, _F, _F, _F, _I, _F, _P]),
     "sonar_brownian_f32": (_I, [_P, _I64, _I64, _P, _P, _I, _U64, _P, _I64, _P]),
     "sonar_brownian_bridge_acc_f32": (_I, [_P, _P, _P, _F, _P, _F, _P, _F, _I64, _I64, _P, _P, _I, _U64, _P, _I64, _P]),
     "sonar_philox_normal_acc_f32": (_I, [_P, _I64, _U64, _U64, _I64, _P]),
@@ -834,6 +836,58 @@ def philox_noise(uniform: bool, shape, device, seed: int, stream_id: int, elem_o
     _check(load().sonar_philox_noise_f32(int(bool(uniform)), _dev(out, "out"), out.numel(), seed & (2**64 - 1), stream_id, elem_offset,
                                          float(sub), float(mul), float(add), float(factor), float(threshold_std_devs), ws.data_ptr(), _stream()),
            "sonar_philox_noise_f32")
+    return out
+
+
+ROWS_NORM_NONE, ROWS_NORM_SCALE_NOISE, ROWS_NORM_FUSED = 0, 1, 2  # SONAR_ROWS_NORM_*
+
+
+def _row_keys(values, rows: int, device, name: str) -> torch.Tensor:
+    """``rows`` 64-bit keys on the device: a device int64 / uint64 tensor as it is, a host sequence uploaded without blocking."""
+    if isinstance(values, torch.Tensor):
+        if values.dtype not in (torch.int64, torch.uint64):
+            raise SonarHipError(f"{name}: expected int64 or uint64, got {values.dtype}")
+        if not values.is_cuda:
+            raise SonarHipError(f"{name}: tensor lives on {values.device}; hand a host sequence or a tensor on the ROCm device")
+        if values.ndim != 1 or values.numel() != rows or not values.is_contiguous():
+            raise SonarHipError(f"{name}: expected {rows} contiguous values, got shape {tuple(values.shape)}")
+        return values
+    vals = [int(v) & _M64 for v in values]
+    if len(vals) != rows:
+        raise SonarHipError(f"{name}: expected {rows} values, got {len(vals)}")
+    host = torch.tensor([v - (1 << 64) if v >> 63 else v for v in vals], dtype=torch.int64)  # (the bit patterns, as int64)
+    return host.pin_memory().to(device, non_blocking=True) if rows else host.to(device)
+
+
+def philox_rows(uniform: bool, shape, device, row_seeds, stream_id: int, factor: float, normalized, *, sub=0.0, mul=1.0, add=0.0,
+                threshold_std_devs: float = 2.5, row_streams=None, out=None) -> torch.Tensor:
+    """``shape[0]`` latents of ``prod(shape[1:])`` elements, row r drawn with (``row_seeds[r]``, ``stream_id + row_streams[r]``) and
+    normalised over itself, in ONE launch: per row the bits of ``philox_normal`` / ``philox_uniform`` on a tensor of its own followed by
+    ``normalized`` False / ROWS_NORM_NONE: ``* factor``; True / ROWS_NORM_SCALE_NOISE: ``scale_noise_(factor, True)`` with the fill's
+    statistics; ROWS_NORM_FUSED: ``philox_noise``'s two-pass form.  ``row_seeds`` / ``row_streams``: a device int64 / uint64 tensor or a host
+    sequence (uploaded non-blocking)."""
+    shape = tuple(int(s) for s in shape)
+    if not shape:
+        raise SonarHipError("philox_rows: the shape needs a leading rows dimension")
+    rows, inner = shape[0], math.prod(shape[1:])
+    mode = int(normalized)
+    if mode not in (ROWS_NORM_NONE, ROWS_NORM_SCALE_NOISE, ROWS_NORM_FUSED):
+        raise SonarHipError(f"philox_rows: unknown normalisation {normalized!r}")
+    if rows < 0 or inner <= 0:
+        raise SonarHipError(f"philox_rows: rows >= 0 and at least one element per row (got shape {shape})")
+    limit = load().sonar_philox_rows_max_inner()
+    if inner > limit:
+        raise SonarHipError(f"philox_rows: at most {limit} elements per row (got {inner})")
+    seeds = _row_keys(row_seeds, rows, device, "philox_rows: row_seeds")
+    streams = None if row_streams is None else _row_keys(row_streams, rows, device, "philox_rows: row_streams")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != shape:
+        raise SonarHipError(f"philox_rows: out has shape {tuple(out.shape)}, expected {shape}")
+    _check(load().sonar_philox_rows_f32(_dev(out, "out"), rows, inner, _dev(seeds, "row_seeds", seeds.dtype),
+                                        None if streams is None else _dev(streams, "row_streams", streams.dtype), int(bool(uniform)),
+                                        int(stream_id) & _M64, float(sub), float(mul), float(add), float(factor), mode,
+                                        float(threshold_std_devs), _stream()), "sonar_philox_rows_f32")
     return out
 
 
@@ -2566,7 +2620,7 @@ PYRAMID_AHEAD = os.environ.get("SONAR_PYRAMID_AHEAD", "1") != "0"  # plans run a
 PERLIN_AHEAD = os.environ.get("SONAR_PERLIN_AHEAD", "1") != "0"  # plans fuse a normalised Perlin call's three launches (_PerlinAheadHook)
 NOT_RUN = object()      # Plan.run: the step was not issued (a guard changed, an entry point refused): take the ordinary path
 _M64 = 2**64 - 1
-_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_power_any_plan", "sonar_dwt_out_len", "sonar_freeu_hidden_mean_groups",
+_HOST_QUERIES = frozenset(("sonar_abi_version", "sonar_noise_stream_version", "sonar_last_error", "sonar_noise_params_ws_doubles", "sonar_group_stats_ws_doubles", "sonar_power_noise_ahead_ok", "sonar_perlin_noise_ahead_ok", "sonar_philox_noise_ahead_ok", "sonar_philox_rows_max_inner", "sonar_power_pipeline", "sonar_wcfg_hi_storage", "sonar_power_plane_kind", "sonar_power_any_plan", "sonar_dwt_out_len", "sonar_freeu_hidden_mean_groups",
                            "sonar_dwt2_ws_bytes", "sonar_wcfg_lowpass_lds_bytes", "sonar_wcfg_fused_ws_bytes", "sonar_pyramid_levels", "sonar_pyramid_route",
                            "sonar_plan_fn_id", "sonar_plan_fn_nargs"))
 PATCH_SLOT, PATCH_STREAM, PATCH_SEED, PATCH_BLOB, PATCH_LEVELS = range(5)

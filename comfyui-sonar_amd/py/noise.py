@@ -176,6 +176,63 @@ class CustomNoiseChain:
         return result
 
     @torch.no_grad()
+    def make_row_seeded_sampler(self, x: Tensor, seeds, *, normalized, cpu=False, positions=None, multiplier=1.0) -> Optional[Callable]:
+        """The per-index loop of ``CustomNOISE.generate_noise`` (a fresh batch-1 sampler per ``seed=seeds[r]``, one call each, then
+        ``* multiplier``) as ONE launch of ``hip_lib.philox_rows``: a callable (sigma, sigma_next) -> fp32 ``[len(seeds), *x.shape[1:]]`` on
+        the device, row r the loop's tensor for its ``positions[r]``-th sampler (default: r) to the bit -- or None when the chain is not one
+        the row kernel reproduces exactly, and the caller keeps its loop.
+
+        What the loop's draw is keyed by: a generate-mode Gaussian / uniform generator never looks at its ``seed=``; it takes (seed, stream
+        id) from the process's device generator (``DeviceRNG.take``), one stream id per call.  After ``torch.manual_seed(s)`` the loop's
+        p-th sampler therefore draws with (s, p) -- skipped indices included, they move the position -- and so does row r here with
+        p = ``positions[r]``; the call takes ``max(positions) + 1`` stream ids, which leaves the generator where the loop leaves it.
+        ``seeds`` fixes the row count and is otherwise what it is to those generators: unused.
+
+        Folded into the launch: the normalisation of a normalised chain whose item factor is 1 (``generate_normalized``: scale_noise's own
+        sequence for N(0,1), the two-pass fill's for uniform draws), and the first multiplier other than 1 of item factor, chain factor
+        and ``multiplier``.  Each further multiplier is a rounding of its own in the loop and stays one: a ``scale_noise_`` launch over all
+        rows.  A normalised chain with an item factor other than 1 normalises the SCALED tensor from a separate statistics sweep
+        (``hip_lib.stats``: another summation order) -- not reproduced, None."""
+        if cpu or len(self.items) != 1 or not torch.is_tensor(x) or x.ndim < 2:
+            return None
+        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            return None
+        item = self.items[0]
+        if type(item) is not CustomNoiseItem or item.noise_type not in (NoiseType.GAUSSIAN, NoiseType.UNIFORM):
+            return None
+        if getattr(item, "ns_kwargs", None) or getattr(item, "normalize", None) is not None:
+            return None  # yaml parameters and an item-level normalisation change what a sampler draws or when it normalises
+        rows = len(seeds)
+        positions = list(range(rows)) if positions is None else [int(p) for p in positions]
+        if len(positions) != rows or rows == 0 or min(positions) < 0:
+            return None
+        uniform = item.noise_type == NoiseType.UNIFORM
+        affine = {k: v for k, v in UniformNoiseGenerator.ng_params().items() if k in ("sub_fac", "mul_fac", "mean_fac")} if uniform else {}
+        item_factor, chain_factor, multiplier = float(item.factor), float(self.factor), float(multiplier)
+        if normalized:
+            if item_factor != 1.0:
+                return None
+            mode = hip_lib.ROWS_NORM_FUSED if uniform else hip_lib.ROWS_NORM_SCALE_NOISE
+            pending = [multiplier]  # (the chain factor, 1, is the normalisation's own multiply: skipped there, skipped here)
+        else:
+            mode = hip_lib.ROWS_NORM_NONE
+            pending = [item_factor, chain_factor, multiplier]
+        pending = [m for m in pending if m != 1.0]
+        shape = (rows, *x.shape[1:])
+        device = x.device
+
+        def noise_sampler(_sigma=None, _sigma_next=None):
+            seed, stream = DeviceRNG.take(max(positions) + 1)
+            out = hip_lib.philox_rows(uniform, shape, device, [seed] * rows, stream, pending[0] if pending else 1.0, mode,
+                                      sub=affine.get("sub_fac", 0.0), mul=affine.get("mul_fac", 1.0), add=affine.get("mean_fac", 0.0),
+                                      row_streams=positions)
+            for m in pending[1:]:
+                hip_lib.scale_noise_(out, m, False, None)
+            return out
+
+        return noise_sampler
+
+    @torch.no_grad()
     def make_noise_sampler(self, x: Tensor, sigma_min=None, sigma_max=None, seed=None, cpu=True, normalized=True) -> Callable:
         if torch.is_tensor(x) and x.dtype in (torch.float16, torch.bfloat16):
             return _for_latent_dtype(x, lambda x32: self.make_noise_sampler(x32, sigma_min, sigma_max, seed=seed, cpu=cpu, normalized=normalized))

@@ -695,6 +695,27 @@ int sonar_philox_noise_ahead_ok(int uniform, int64_t n, float factor);
 int sonar_philox_noise_ahead_f32(int uniform, float* out, int64_t n, uint64_t seed, uint64_t stream_id, int64_t elem_offset,
                                  float sub, float mul, float add, float factor, float threshold_std_devs, double* partials,
                                  int have_stats, uint64_t next_stream_id, double* partials_next, void* stream);
+/* `rows` independent latents of `inner` contiguous elements from ONE launch (csrc/noise_rows.hip; the batch_index form of
+ * CustomNOISE.generate_noise).  Row r is, bit for bit, what a call on a 16-byte aligned tensor of its own gives:
+ *   sonar_philox_normal_f32 / sonar_philox_uniform_f32(x_r, inner, row_seed[r], stream_id + row_stream[r], 0, partials_r), then
+ *   SONAR_ROWS_NORM_NONE         x_r *= factor (skipped for a factor of exactly 1)
+ *   SONAR_ROWS_NORM_SCALE_NOISE  sonar_scale_noise_f32(x_r, inner, factor, 1, threshold_std_devs, partials_r, SONAR_NPART, inner)
+ *   SONAR_ROWS_NORM_FUSED        the final pass of sonar_philox_noise_f32's two-pass route (uniform draws, and normal draws with a factor
+ *                                other than 1): the same statistics and decision, the quotient as a multiply by 1 / std
+ * -- mean, unbiased std and both thresholds (threshold_std_devs / sqrt(inner)) are the row's own, from the fp64 (sum, sumsq) partials in the
+ * order the per-call fill reduces `inner` elements.  row_seed, row_stream: DEVICE arrays of `rows` values; row_stream may be NULL (every row
+ * draws with stream_id).  sub, mul, add: sonar_philox_uniform_f32's affine map, ignored for normal draws.  One workgroup per row, no
+ * workspace, no atomics.
+ * SONAR_ERR_UNSUPPORTED, nothing launched: rows < 0, inner <= 0, inner > sonar_philox_rows_max_inner() (SONAR_NPART * 4 tiles of 4096),
+ * row_seed NULL with rows > 0.  SONAR_ERR_ARG: an unknown normalisation, out NULL or not aligned to a float.  rows == 0: success, nothing
+ * launched. */
+#define SONAR_ROWS_NORM_NONE 0
+#define SONAR_ROWS_NORM_SCALE_NOISE 1
+#define SONAR_ROWS_NORM_FUSED 2
+int64_t sonar_philox_rows_max_inner(void);
+int sonar_philox_rows_f32(float* out, int64_t rows, int64_t inner, const uint64_t* row_seed, const uint64_t* row_stream /*nullable*/,
+                          int uniform, uint64_t stream_id, float sub, float mul, float add, float factor, int normalized,
+                          float threshold_std_devs, void* stream);
 
 /* Brownian-interval noise (the reference wraps ComfyUI's BrownianTreeNoiseSampler -> torchsde, un-vendored:
  * py/noise_generation.py:262-286, py/nodes/powernoise.py:383-393).  out[e] = sum_k coefs[k] * z(node_ids[k], e) with
