@@ -116,6 +116,7 @@ SIGNATURES = {
     "sonar_philox_noise_ahead_f32": (_I, [_I, _P, _I64, _U64, _U64, _I64, _F, _F, _F, _F, _F, _P, _I, _U64, _P, _P]),
     "sonar_philox_rows_max_inner": (_I64, []),
     "sonar_philox_rows_f32": (_I, [_P, _I64, _I64, _P, _P, _I, _U64, _F, _F, _F, _F, _I, _F, _P]),
+    "sonar_perlin_rows_f32": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _I, _F, _P, _P, _U64, _F, _I, _F, _P]),
     "sonar_brownian_f32": (_I, [_P, _I64, _I64, _P, _P, _I, _U64, _P, _I64, _P]),
     "sonar_brownian_bridge_acc_f32": (_I, [_P, _P, _P, _F, _P, _F, _P, _F, _I64, _I64, _P, _P, _I, _U64, _P, _I64, _P]),
     "sonar_philox_normal_acc_f32": (_I, [_P, _I64, _U64, _U64, _I64, _P]),
@@ -888,6 +889,47 @@ def philox_rows(uniform: bool, shape, device, row_seeds, stream_id: int, factor:
                                         None if streams is None else _dev(streams, "row_streams", streams.dtype), int(bool(uniform)),
                                         int(stream_id) & _M64, float(sub), float(mul), float(add), float(factor), mode,
                                         float(threshold_std_devs), _stream()), "sonar_philox_rows_f32")
+    return out
+
+
+def perlin_rows(shape, device, row_seeds, stream_id: int, *, iterations: int, div_fac: float, blend_mode: str, factor: float, normalized,
+                row_streams=None, out=None, lattice=None, threshold_std_devs: float = 2.5) -> torch.Tensor:
+    """``shape`` = (rows, C, H, W): row r is generate-mode Perlin noise of ONE latent drawn with (``row_seeds[r]``, s) and a lattice of
+    its own drawn with (``row_seeds[r]``, s + 1), s = ``stream_id + row_streams[r]``, in ONE launch: per row the bits of
+    ``perlin_lattice`` followed by ``normalized`` False / ROWS_NORM_NONE: ``perlin_generate`` and ``* factor``; True / ROWS_NORM_FUSED:
+    ``perlin_noise(..., factor)``, each on tensors of their own.  ``lattice``: the [rows, C, H, W] workspace the rows' lattices are left
+    in (allocated when None).  ``row_seeds`` / ``row_streams`` as in ``philox_rows``."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 4:
+        raise SonarHipError(f"perlin_rows: the shape is (rows, C, H, W) (got {shape})")
+    rows, inner = shape[0], math.prod(shape[1:])
+    if normalized is True or normalized is False:
+        mode = ROWS_NORM_FUSED if normalized else ROWS_NORM_NONE
+    else:
+        mode = int(normalized)
+    if mode not in (ROWS_NORM_NONE, ROWS_NORM_FUSED):
+        raise SonarHipError(f"perlin_rows: unknown normalisation {normalized!r}")
+    if blend_mode not in BLEND_IDS:
+        raise SonarHipError(f"perlin_rows: unknown blend mode {blend_mode!r}")
+    if rows < 0 or inner <= 0:
+        raise SonarHipError(f"perlin_rows: rows >= 0 and at least one element per row (got shape {shape})")
+    limit = load().sonar_philox_rows_max_inner()
+    if inner > limit:
+        raise SonarHipError(f"perlin_rows: at most {limit} elements per row (got {inner})")
+    seeds = _row_keys(row_seeds, rows, device, "perlin_rows: row_seeds")
+    streams = None if row_streams is None else _row_keys(row_streams, rows, device, "perlin_rows: row_streams")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != shape:
+        raise SonarHipError(f"perlin_rows: out has shape {tuple(out.shape)}, expected {shape}")
+    if lattice is None:
+        lattice = torch.empty(shape, dtype=torch.float32, device=device)
+    elif tuple(lattice.shape) != shape:
+        raise SonarHipError(f"perlin_rows: lattice has shape {tuple(lattice.shape)}, expected {shape}")
+    _check(load().sonar_perlin_rows_f32(_dev(out, "out"), _dev(lattice, "lattice"), rows, shape[1], shape[2], shape[3], max(int(iterations), 0),
+                                        BLEND_IDS[blend_mode], float(div_fac), _dev(seeds, "row_seeds", seeds.dtype),
+                                        None if streams is None else _dev(streams, "row_streams", streams.dtype), int(stream_id) & _M64,
+                                        float(factor), mode, float(threshold_std_devs), _stream()), "sonar_perlin_rows_f32")
     return out
 
 

@@ -192,13 +192,15 @@ class CustomNoiseChain:
         sequence for N(0,1), the two-pass fill's for uniform draws), and the first multiplier other than 1 of item factor, chain factor
         and ``multiplier``.  Each further multiplier is a rounding of its own in the loop and stays one: a ``scale_noise_`` launch over all
         rows.  A normalised chain with an item factor other than 1 normalises the SCALED tensor from a separate statistics sweep
-        (``hip_lib.stats``: another summation order) -- not reproduced, None."""
+        (``hip_lib.stats``: another summation order) -- not reproduced, None.
+
+        A chain of one plain Perlin item goes the same way through ``hip_lib.perlin_rows`` (``_perlin_row_sampler`` has its keys)."""
         if cpu or len(self.items) != 1 or not torch.is_tensor(x) or x.ndim < 2:
             return None
         if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             return None
         item = self.items[0]
-        if type(item) is not CustomNoiseItem or item.noise_type not in (NoiseType.GAUSSIAN, NoiseType.UNIFORM):
+        if type(item) is not CustomNoiseItem or item.noise_type not in (NoiseType.GAUSSIAN, NoiseType.UNIFORM, NoiseType.PERLIN):
             return None
         if getattr(item, "ns_kwargs", None) or getattr(item, "normalize", None) is not None:
             return None  # yaml parameters and an item-level normalisation change what a sampler draws or when it normalises
@@ -206,6 +208,8 @@ class CustomNoiseChain:
         positions = list(range(rows)) if positions is None else [int(p) for p in positions]
         if len(positions) != rows or rows == 0 or min(positions) < 0:
             return None
+        if item.noise_type == NoiseType.PERLIN:
+            return self._perlin_row_sampler(x, rows, positions, normalized, float(multiplier))
         uniform = item.noise_type == NoiseType.UNIFORM
         affine = {k: v for k, v in UniformNoiseGenerator.ng_params().items() if k in ("sub_fac", "mul_fac", "mean_fac")} if uniform else {}
         item_factor, chain_factor, multiplier = float(item.factor), float(self.factor), float(multiplier)
@@ -229,6 +233,51 @@ class CustomNoiseChain:
             for m in pending[1:]:
                 hip_lib.scale_noise_(out, m, False, None)
             return out
+
+        return noise_sampler
+
+    def _perlin_row_sampler(self, x: Tensor, rows: int, positions, normalized, multiplier: float) -> Optional[Callable]:
+        """``make_row_seeded_sampler`` for a chain of one plain Perlin item: ONE launch of ``hip_lib.perlin_rows``.
+
+        A generate-mode ``PerlinOldNoiseGenerator`` takes ``device_key(2)`` per call -- the values on (seed, stream), the lattice on
+        (seed, stream + 1) -- so after ``torch.manual_seed(s)`` the loop's p-th sampler draws with stream ids 2p and 2p + 1: row r gets
+        ``2 * positions[r]``, and the call takes ``2 * (max(positions) + 1)`` ids.  Every batch-1 call of the loop has a lattice of its
+        own, hence one per row.  A 5-D latent folds its frames into the channels (``get_adjusted_shape``) and is reshaped back.  A
+        normalised chain (item factor 1) is ``generate_normalized``: ``perlin_noise`` with the chain factor 1, then ``* multiplier`` --
+        the multiplier rides as the final pass's factor, the same two roundings.  Unnormalised: the raw values, then item factor, chain
+        factor and multiplier as in the Gaussian route.  None for what the loop computes otherwise: a sharded batch (the loop's element
+        offset is the shard's), a latent longer than the row kernel takes, and a latent in host memory: the launch and its lattice
+        workspace live on ``x``'s device, and ``PerlinOldNoiseGenerator`` refuses a host latent -- the loop is left to say so."""
+        if x.ndim not in (4, 5) or current_batch_offset() != 0 or x.device.type == "cpu":
+            return None
+        params = PerlinOldNoiseGenerator.ng_params()
+        if params["blend_mode"] not in hip_lib.BLEND_IDS:
+            return None
+        c = x.shape[1] * x.shape[2] if x.ndim == 5 else x.shape[1]
+        h, w = x.shape[-2:]
+        chw = c * h * w
+        if chw <= 0 or chw >= 2**31 or chw > hip_lib.NPART * 4 * 4096:  # (sonar_philox_rows_max_inner)
+            return None
+        item_factor, chain_factor = float(self.items[0].factor), float(self.factor)
+        if normalized:
+            if item_factor != 1.0:
+                return None
+            pending = [multiplier]
+        else:
+            pending = [item_factor, chain_factor, multiplier]
+        pending = [m for m in pending if m != 1.0]
+        final_shape = (rows, *x.shape[1:])
+        device = x.device
+        streams = [2 * p for p in positions]
+
+        def noise_sampler(_sigma=None, _sigma_next=None):
+            seed, stream = DeviceRNG.take(2 * (max(positions) + 1))
+            out = hip_lib.perlin_rows((rows, c, h, w), device, [seed] * rows, stream, iterations=params["iterations"], div_fac=params["div_fac"],
+                                      blend_mode=params["blend_mode"], factor=pending[0] if pending else 1.0, normalized=bool(normalized),
+                                      row_streams=streams)
+            for m in pending[1:]:
+                hip_lib.scale_noise_(out, m, False, None)
+            return out.reshape(final_shape)
 
         return noise_sampler
 

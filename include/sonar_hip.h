@@ -716,6 +716,21 @@ int64_t sonar_philox_rows_max_inner(void);
 int sonar_philox_rows_f32(float* out, int64_t rows, int64_t inner, const uint64_t* row_seed, const uint64_t* row_stream /*nullable*/,
                           int uniform, uint64_t stream_id, float sub, float mul, float add, float factor, int normalized,
                           float threshold_std_devs, void* stream);
+/* The same for generate-mode Perlin noise: `rows` latents of C * H * W elements, every row with its OWN lattice.  Row r is, bit for bit,
+ * what these calls give on 16-byte aligned tensors of their own, with s_r = stream_id + row_stream[r]:
+ *   sonar_perlin_lattice_f32(terms_r, iters, C, H, W, blend_mode, row_seed[r], s_r + 1), then
+ *   SONAR_ROWS_NORM_NONE   sonar_perlin_generate_f32(terms_r, x_r, 1, C * H * W, 1, div_fac, row_seed[r], s_r, 0, ...), x_r *= factor (skipped
+ *                          for a factor of exactly 1)
+ *   SONAR_ROWS_NORM_FUSED  sonar_perlin_noise_f32(terms_r, x_r, 1, C * H * W, 1, div_fac, row_seed[r], s_r, 0, factor, threshold_std_devs, ...)
+ * -- the launch route (scalar, vector, fast, tile-aligned), the word-to-value converter and the order of the (sum, sumsq) partials are
+ * those of a batch of ONE latent of C * H * W elements, whatever the address of the row inside `out`.  lattice: workspace of rows * C * H * W
+ * floats, 16-byte aligned; row r's summed lattice is left in its slice.  One workgroup per row, no atomics.
+ * SONAR_ERR_UNSUPPORTED, nothing launched: rows < 0, H or W >= 2^20, C * H * W > sonar_philox_rows_max_inner(), row_seed NULL with rows > 0.
+ * SONAR_ERR_ARG: C, H or W <= 0, iters < 0 or >= 2^20, an unknown blend mode, a normalisation other than the two above, out NULL or not
+ * aligned to a float, lattice NULL or not 16-byte aligned, lattice == out.  rows == 0: success, nothing launched. */
+int sonar_perlin_rows_f32(float* out, float* lattice, int64_t rows, int64_t C, int64_t H, int64_t W, int64_t iters, int blend_mode,
+                          float div_fac, const uint64_t* row_seed, const uint64_t* row_stream /*nullable*/, uint64_t stream_id,
+                          float factor, int normalized, float threshold_std_devs, void* stream);
 
 /* Brownian-interval noise (the reference wraps ComfyUI's BrownianTreeNoiseSampler -> torchsde, un-vendored:
  * py/noise_generation.py:262-286, py/nodes/powernoise.py:383-393).  out[e] = sum_k coefs[k] * z(node_ids[k], e) with
